@@ -12,8 +12,21 @@ accounting for "Atari MsPacman 100K frames in 14h on 1x RTX 3080"
  = 400k env frames / 50400 s = 7.94 env-frames/s.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
 For N>1 the driver launches this under torch.distributed.run (one rank/GPU,
 RCCL over xGMI); each rank runs an identical replica (weak scaling, DP).
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line.  ``--dump-outputs DIR`` additionally
+writes what the last timed step computed as ``DIR/<name>.npy``.  So that two
+runs, or two builds, can be compared output for output, that last step of a
+dump run starts from a seeded snapshot (initial parameters, fresh optimizer
+and RNG state, a batch sampled before any training): the HIP kernels
+accumulate split-K partials, LayerNorm weight grads and loss sums with fp32
+atomic adds whose order varies, which makes one step reproducible to bf16
+rounding, and a chain of training steps amplifies that.  ``--full`` adds
+the work that is not needed for the headline figure: the hipBLASLt TunableOp
+sweep before the warmup.
 """
 
 from __future__ import annotations
@@ -31,6 +44,76 @@ import numpy as np
 import torch
 
 BASELINE_ENV_FRAMES_PER_SEC = 400_000 / (14 * 3600)  # RTX 3080, BASELINE.md row 2
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: total size of the .npy files
+
+
+def _flat_params(module) -> torch.Tensor:
+    return torch.cat([p.detach().reshape(-1).float() for p in module.parameters()])
+
+
+class _SeededSnapshot:
+    """--dump-outputs: the state that the last timed step of a dump run starts
+    from.  The kernels' fp32 atomic accumulations make one gradient step
+    reproducible to bf16 rounding only, and a chain of training steps
+    amplifies that; taken after the seeded setup and before any gradient
+    step, this snapshot is the same in every run and in every build, so the
+    dumped outputs differ by one step's rounding at the most."""
+
+    def __init__(self, modules, optims, device) -> None:
+        self.modules, self.optims, self.device = modules, optims, device
+        self.tensors = [[t.detach().clone() for t in (*m.parameters(), *m.buffers())] for m in modules]
+        self.cpu_rng = torch.get_rng_state()
+        self.dev_rng = torch.cuda.get_rng_state(device) if device.type == "cuda" else None
+
+    def restore(self) -> float:
+        """Put the state back in place (hipGraph-captured addresses stay
+        valid); returns the seconds it took, to keep them out of the timing."""
+        cuda = self.device.type == "cuda"
+        if cuda:
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            for m, saved in zip(self.modules, self.tensors):
+                for t, s in zip((*m.parameters(), *m.buffers()), saved):
+                    t.copy_(s)
+            # a fresh optimizer: zero moments (RMSpropTF: unit square_avg) and
+            # zero step counts, on the host and on the device
+            for opt in self.optims:
+                for st in opt.state.values():
+                    for k, v in st.items():
+                        if isinstance(v, torch.Tensor):
+                            v.fill_(1.0) if k == "square_avg" else v.zero_()
+                        elif k == "step":
+                            st[k] = 0
+        torch.set_rng_state(self.cpu_rng)
+        if cuda:
+            torch.cuda.set_rng_state(self.dev_rng, self.device)
+            torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+
+def _dump_outputs(dump_dir, outputs) -> None:
+    """Write ``outputs`` (name -> tensor/array) as float32 ``<name>.npy``.
+
+    The byte budget is shared smallest-first: an array within an equal
+    share of what is left is written whole, a larger one is reduced to a
+    fixed, seeded sample of its flattened elements (same indices for the
+    same sizes, so two builds stay comparable)."""
+    out = Path(dump_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {}
+    for name, v in outputs.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().float().cpu().numpy()
+        arrays[name] = np.ascontiguousarray(v, dtype=np.float32)
+    left = (DUMP_BUDGET_BYTES - 1024 * len(arrays)) // 4  # elements; 1 KiB per file for the header
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].size)):
+        cap = left // (len(arrays) - i)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.size
+        np.save(out / f"{name}.npy", a)
 
 
 def _build(cfg_overrides, device_type: str):
@@ -142,7 +225,7 @@ def _prefill(cfg, envs, rb, n_steps: int):
     return obs, step_data
 
 
-def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
+def run_bench(n_gpus: int, steps: int, warmup: int, overrides=(), dump_dir=None, full: bool = False) -> dict:
     import torch.distributed as dist
 
     from sheeprl_amd.algos.dreamer_v3.dreamer_v3 import train
@@ -160,9 +243,10 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
             raise RuntimeError("HIP extension _sheep_hip is not built — refusing to bench the eager fallback")
         # hipBLASLt algorithm tuning during the (untimed) warmup: the scan's
         # M=16 long-K GEMMs gain ~1 ms/step on XL from better algo picks
-        # (neutral on S, measured).  Single-rank only — tuning sweeps would
-        # desync multi-rank warmup; opt out with SHEEPRL_AMD_TUNABLEOP=0.
-        if world_size == 1 and os.environ.get("SHEEPRL_AMD_TUNABLEOP", "1") != "0":
+        # (neutral on S, measured), so only a --full run pays for the sweep.
+        # Single-rank only — tuning sweeps would desync multi-rank warmup;
+        # opt out with SHEEPRL_AMD_TUNABLEOP=0.
+        if full and world_size == 1 and os.environ.get("SHEEPRL_AMD_TUNABLEOP", "1") != "0":
             try:
                 import torch.cuda.tunable as tunable
 
@@ -182,6 +266,14 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
 
     obs, step_data = _prefill(cfg, envs, rb, n_steps=max(seq_len + 1, 80))
     player.init_states()
+
+    # --dump-outputs: the last timed step starts from this seeded state and
+    # from a batch sampled here, before any gradient step
+    snap = snap_batch = None
+    if dump_dir:
+        snap = _SeededSnapshot((world_model, actor, critic, target_critic, moments), optims, device)
+        snap_batch = {k: v[0].clone() for k, v in rb.sample_tensors(
+            cfg.algo.per_rank_batch_size, sequence_length=seq_len, n_samples=1, device=device).items()}
 
     aggregator = MetricAggregator({})
     MetricAggregator.disabled = True
@@ -265,11 +357,17 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
             self.h[:, reset_envs] = rec.to(self.h.dtype)
             self.z[:, reset_envs] = stoch.reshape(1, len(reset_envs), -1).to(self.z.dtype)
 
+    # --dump-outputs: train() stashes references to its loss tensors here
+    # (static buffers under hipGraph capture, refreshed by every replay)
+    metrics_out = {} if dump_dir else None
+    last = {}
+
     def train_fn(batch):
         train(
             runtime, world_model, actor, critic, target_critic,
             world_optimizer, actor_optimizer, critic_optimizer,
             batch, aggregator, cfg, False, actions_dim, moments,
+            metrics_out=metrics_out,
         )
 
     # hipGraph-capture the whole gradient step (fwd+bwd+optimizers): the
@@ -306,7 +404,7 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
             if rank == 0:
                 print(f"[bench] player graph capture failed ({e}); eager player", file=sys.stderr)
 
-    def one_iter(obs, step_data):
+    def one_iter(obs, step_data, fixed_batch=None):
         # --- env interaction (the real policy forward + env step + buffer add)
         with torch.inference_mode():
             torch_obs = prepare_obs(runtime, obs, cnn_keys=list(cfg.algo.cnn_keys.encoder), num_envs=num_envs)
@@ -314,6 +412,7 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
             actions = torch.cat(acts, -1).view(num_envs, -1).float().cpu().numpy()
             real_actions = torch.stack([a.argmax(dim=-1) for a in acts], dim=-1).view(num_envs).cpu().numpy()
         step_data["actions"] = actions[None]
+        last["actions"] = actions
         if prefetcher is not None:
             with prefetcher.lock:
                 rb.add(step_data)
@@ -339,7 +438,10 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
         from sheeprl_amd import ops as _ops
 
         _ops.ema_update_(list(target_critic.parameters()), list(critic.parameters()), cfg.algo.critic.tau)
-        if prefetcher is not None:
+        if fixed_batch is not None:
+            # eager train() edits its batch in place: hand it a copy
+            batch = {k: v.clone() for k, v in fixed_batch.items()}
+        elif prefetcher is not None:
             batch = prefetcher.next()
         elif gatherer is not None:
             batch = {k: v[0] for k, v in gatherer.next().items()}
@@ -404,13 +506,22 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
     if device_type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        obs = one_iter(obs, step_data)
+    t_restore = 0.0
+    for i in range(steps):
+        if snap is not None and i == steps - 1:
+            # dump run: the last timed step starts from the seeded snapshot;
+            # the restore itself is kept out of the timed figure
+            t_restore = snap.restore()
+            with torch.inference_mode():
+                (gplayer or player).init_states(list(range(num_envs)))
+            obs = one_iter(obs, step_data, snap_batch)
+        else:
+            obs = one_iter(obs, step_data)
     if device_type == "cuda":
         torch.cuda.synchronize()
     if runtime.is_distributed:
         dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - t_restore
     if runtime.is_distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if runtime.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -418,6 +529,15 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
 
     if prefetcher is not None:
         prefetcher.close()
+    if dump_dir and rank == 0:
+        # what the last timed step handed back: the policy's actions, the
+        # gradient step's losses, and the parameters it left behind
+        outputs = {"player_actions": last["actions"]} if "actions" in last else {}
+        outputs.update({f"train_{k}": v for k, v in metrics_out.items()})
+        outputs["params_world_model"] = _flat_params(world_model)
+        outputs["params_actor"] = _flat_params(actor)
+        outputs["params_critic"] = _flat_params(critic)
+        _dump_outputs(dump_dir, outputs)
     policy_steps = steps * num_envs * world_size
     env_frames_per_sec = policy_steps * cfg.env.action_repeat / elapsed
     result = {
@@ -449,7 +569,7 @@ def run_bench(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
     return result
 
 
-def run_bench_sac(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
+def run_bench_sac(n_gpus: int, steps: int, warmup: int, overrides=(), dump_dir=None) -> dict:
     """SAC on a HalfCheetah-shaped synthetic env (17-dim obs, 6-dim actions),
     bf16 on GPU — BASELINE.json config #2.  One step = one vectorized env
     interaction + the replay-ratio-driven gradient step (batch 256), with the
@@ -538,6 +658,12 @@ def run_bench_sac(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
     aggregator = MetricAggregator({})
     MetricAggregator.disabled = True
     update = [0]
+    # --dump-outputs: the last timed step starts from this seeded state and
+    # from a batch sampled here, before any gradient step
+    snap = snap_batch = None
+    if dump_dir:
+        snap = _SeededSnapshot((agent, player), (qf_optimizer, actor_optimizer, alpha_optimizer), device)
+        snap_batch = {k: v[0].clone() for k, v in rb.sample_tensors(bs, n_samples=1, device=device).items()}
 
     def train_fn(batch):
         update[0] += 1
@@ -566,12 +692,18 @@ def run_bench_sac(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
             if rank == 0:
                 print(f"[bench] hipGraph capture failed ({e}); running eager", file=sys.stderr)
 
-    def one_iter():
+    last = {}
+
+    def one_iter(fixed_batch=None):
         with torch.no_grad():
             t_obs = torch.as_tensor(obs, device=device, dtype=torch.float32).to(pdt)
             actions = player.get_actions(t_obs).float().cpu().numpy()
+        last["actions"] = actions
         env_step(actions)
-        batch = cast_batch({k: v[0] for k, v in rb.sample_tensors(bs, n_samples=1, device=device).items()})
+        if fixed_batch is not None:
+            batch = cast_batch({k: v.clone() for k, v in fixed_batch.items()})
+        else:
+            batch = cast_batch({k: v[0] for k, v in rb.sample_tensors(bs, n_samples=1, device=device).items()})
         if graphed is not None:
             graphed(batch)
         else:
@@ -584,18 +716,28 @@ def run_bench_sac(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
     if device_type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        one_iter()
+    t_restore = 0.0
+    for i in range(steps):
+        if snap is not None and i == steps - 1:
+            t_restore = snap.restore()
+            update[0] = 0
+            one_iter(snap_batch)
+        else:
+            one_iter()
     if device_type == "cuda":
         torch.cuda.synchronize()
     if runtime.is_distributed:
         dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - t_restore
     if runtime.is_distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if runtime.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     envs.close()
+    if dump_dir and rank == 0:
+        outputs = {"player_actions": last["actions"]} if "actions" in last else {}
+        outputs["params_agent"] = _flat_params(agent)
+        _dump_outputs(dump_dir, outputs)
     fps = steps * num_envs * world_size / elapsed
     return {
         "metric": "env_frames_per_sec",
@@ -622,7 +764,7 @@ def run_bench_sac(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
     }
 
 
-def run_bench_ppo(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
+def run_bench_ppo(n_gpus: int, steps: int, warmup: int, overrides=(), dump_dir=None) -> dict:
     """PPO on the synthetic Atari-shaped env (3x64x64 uint8, 9 actions),
     bf16 on GPU.  One step = one full PPO iteration: rollout_steps env
     interactions per env + GAE + update_epochs x minibatch SGD, the
@@ -687,6 +829,8 @@ def run_bench_ppo(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
     action_space = envs.single_action_space
     agent, player = build_ppo(runtime, obs_space, action_space, cfg, None)
     optimizer = make_optimizer(agent.parameters(), cfg.algo.optimizer)
+    # --dump-outputs: the last timed iteration starts from this seeded state
+    snap = _SeededSnapshot((agent, player), (optimizer,), device) if dump_dir else None
 
     # device-side rollout storage (obs stay uint8; encoder normalizes on GPU)
     store = {
@@ -800,8 +944,11 @@ def run_bench_ppo(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
     gen = torch.Generator(device=device)
     gen.manual_seed(cfg.seed + rank)
 
+    last = {}
+
     def one_iter():
         data = rollout()
+        last["data"] = data
         for _ in range(cfg.algo.update_epochs):
             perm = torch.randperm(rows, device=device, generator=gen)
             for s in range(0, rows, bs):
@@ -819,18 +966,27 @@ def run_bench_ppo(n_gpus: int, steps: int, warmup: int, overrides=()) -> dict:
     if device_type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    t_restore = 0.0
+    for i in range(steps):
+        if snap is not None and i == steps - 1:
+            t_restore = snap.restore()
+            gen.manual_seed(cfg.seed + rank)
         one_iter()
     if device_type == "cuda":
         torch.cuda.synchronize()
     if runtime.is_distributed:
         dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - t_restore
     if runtime.is_distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if runtime.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     envs.close()
+    if dump_dir and rank == 0:
+        # the last iteration's rollout results and the parameters it left
+        outputs = {f"rollout_{k}": v for k, v in last.get("data", {}).items() if k != "obs_rgb"}
+        outputs["params_agent"] = _flat_params(agent)
+        _dump_outputs(dump_dir, outputs)
     fps = steps * rows * world_size / elapsed
     return {
         "metric": "env_frames_per_sec",
@@ -885,14 +1041,20 @@ def main() -> None:
                    help="flagship DV3 Atari-100K (default), SAC HalfCheetah-shape (BASELINE #2), "
                         "or PPO pixels (synthetic Atari shape)")
     p.add_argument("--override", action="append", default=[])
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                        "(float32, at most 64 MB in all; larger arrays as a fixed seeded sample)")
+    p.add_argument("--full", action="store_true",
+                   help="also do what the headline figure does not need: the hipBLASLt TunableOp "
+                        "sweep before the warmup (single rank, flagship DV3 only)")
     args = p.parse_args()
     rank = int(os.environ.get("RANK", 0))
     if args.algo == "sac":
-        result = run_bench_sac(args.gpus, args.steps, args.warmup, args.override)
+        result = run_bench_sac(args.gpus, args.steps, args.warmup, args.override, args.dump_outputs)
     elif args.algo == "ppo":
-        result = run_bench_ppo(args.gpus, args.steps, args.warmup, args.override)
+        result = run_bench_ppo(args.gpus, args.steps, args.warmup, args.override, args.dump_outputs)
     else:
-        result = run_bench(args.gpus, args.steps, args.warmup, args.override)
+        result = run_bench(args.gpus, args.steps, args.warmup, args.override, args.dump_outputs, args.full)
     if rank == 0:
         print(json.dumps(result))
 

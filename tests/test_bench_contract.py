@@ -66,6 +66,68 @@ def test_bench_single_rank_default(tmp_path):
 
 
 @pytest.mark.timeout(600)
+def test_bench_full_and_dump_outputs(tmp_path):
+    """`--full --dump-outputs DIR`: same result line, plus the last timed
+    step's outputs as float .npy files within the 64 MB budget."""
+    import numpy as np
+
+    env = dict(os.environ)
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env["PYTHONPATH"] = f"{repo}:{env.get('PYTHONPATH', '')}"
+    dump = tmp_path / "dump"
+    out = subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+         "--full", "--dump-outputs", str(dump), *TINY],
+        capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=570,
+    )
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    json_lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(json_lines) == 1, out.stdout
+    rec = json.loads(json_lines[0])
+    assert rec["metric"] == "env_frames_per_sec" and rec["unit"] == "frames/s"
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["higher_is_better"] is True
+    files = sorted(dump.glob("*.npy"))
+    names = {f.stem for f in files}
+    assert {"player_actions", "train_rec_loss", "train_policy_loss", "train_value_loss",
+            "params_world_model", "params_actor", "params_critic"} <= names, names
+    assert sum(f.stat().st_size for f in files) <= 64 * 1000 * 1000
+    for f in files:
+        a = np.load(f)
+        assert a.dtype in (np.float32, np.float64), (f.name, a.dtype)
+        assert a.size > 0 and np.isfinite(a).all(), f.name
+    # same arguments, second run: the fp32 CPU path has no atomics, so the
+    # outputs must be bit-identical (on the GPU: equal to bf16 rounding)
+    dump2 = tmp_path / "dump2"
+    out2 = subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+         "--dump-outputs", str(dump2), *TINY],
+        capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=570,
+    )
+    assert out2.returncode == 0, out2.stdout[-2000:] + out2.stderr[-2000:]
+    assert {f.name for f in dump2.glob("*.npy")} == {f.name for f in files}
+    for f in files:
+        assert np.array_equal(np.load(f), np.load(dump2 / f.name)), f.name
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path):
+    """An array over its share of the budget is cut to a fixed sample: the
+    same elements on every call, and the whole dump stays within 64 MB."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    big = torch.arange(20_000_000, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench._dump_outputs(tmp_path / d, {"big": big, "big2": big * 2, "small": np.ones((3, 2))})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.size < big.numel() and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "big2.npy"), 2 * a)  # same indices
+    assert np.load(tmp_path / "a" / "small.npy").shape == (3, 2)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").glob("*.npy")) <= 64 * 1000 * 1000
+
+
+@pytest.mark.timeout(600)
 def test_bench_ppo_algo_single_rank(tmp_path):
     """`python bench.py --algo ppo` emits one valid contract JSON line."""
     env = dict(os.environ)
