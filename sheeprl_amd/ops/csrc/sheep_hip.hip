@@ -2688,8 +2688,9 @@ void ema_update(std::vector<torch::Tensor> tgts, std::vector<torch::Tensor> srcs
 // uint8 obs -> float in [-0.5, 0.5]
 // ---------------------------------------------------------------------------
 
-__global__ void obs_norm_kernel(const unsigned char* __restrict__ x, float* __restrict__ y, long n) {
-  const long n4 = n / 4;
+// n4 is the number of leading 4-byte groups read as uchar4 (0 when x is not
+// 4-byte aligned); the scalar loop covers the remaining n - 4*n4 elements.
+__global__ void obs_norm_kernel(const unsigned char* __restrict__ x, float* __restrict__ y, long n, long n4) {
   const uchar4* x4 = reinterpret_cast<const uchar4*>(x);
   float4* y4 = reinterpret_cast<float4*>(y);
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -2705,10 +2706,13 @@ torch::Tensor obs_norm(const torch::Tensor& x) {
   TORCH_CHECK(x.scalar_type() == at::kByte, "obs_norm expects uint8");
   auto y = torch::empty(x.sizes(), x.options().dtype(at::kFloat));
   long n = x.numel();
+  // a contiguous uint8 view may start at any byte: uchar4 loads need alignment
+  const bool aligned = reinterpret_cast<uintptr_t>(x.data_ptr()) % 4 == 0;
+  const long n4 = aligned ? n / 4 : 0;
   int blocks = (int)std::min((n / 4 + kBlock - 1) / kBlock + 1, (long)2048);
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(obs_norm_kernel, dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                     (const unsigned char*)x.data_ptr(), y.data_ptr<float>(), n);
+                     (const unsigned char*)x.data_ptr(), y.data_ptr<float>(), n, n4);
   return y;
 }
 

@@ -149,9 +149,18 @@ def ema_update_(target_params: Iterable[Tensor], source_params: Iterable[Tensor]
     if (
         tgt
         and use_hip(tgt[0])
-        # the HIP kernel walks data_ptr flat: both sides must share the same
-        # dense layout (true for deepcopy/convert pairs; guard the rest)
-        and all(t.stride() == s.stride() for t, s in zip(tgt, src))
+        # the HIP kernel walks numel elements flat from data_ptr and reads
+        # both sides as the target's dtype: each pair must share one dense
+        # layout, dtype and device (true for deepcopy/convert pairs; the rest
+        # take the strided foreach path)
+        and all(
+            t.stride() == s.stride()
+            and t.shape == s.shape
+            and t.dtype == s.dtype
+            and t.device == s.device
+            and (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last))
+            for t, s in zip(tgt, src)
+        )
     ):
         require_ext().ema_update(tgt, src, float(tau))
         return

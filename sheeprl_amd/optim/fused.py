@@ -19,6 +19,33 @@ from torch import Tensor
 from sheeprl_amd.ops._ext import require_ext, use_hip
 
 
+def _reinstall_fp32_state(opt: torch.optim.Optimizer, state_dict: dict) -> None:
+    """Undo ``Optimizer.load_state_dict``'s cast of tensor state to the
+    parameter dtype: re-install every saved tensor as float32 on the
+    parameter's device, bit-identical to what was saved.  The HIP kernels read
+    these buffers as ``float*``; a bf16 copy would be half the size."""
+    saved_ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+    params = [p for g in opt.param_groups for p in g["params"]]
+    for i, p in zip(saved_ids, params):
+        saved = state_dict["state"].get(i)
+        if saved is None:
+            continue
+        st = opt.state[p]
+        for k, v in saved.items():
+            if isinstance(v, Tensor) and v.is_floating_point():
+                st[k] = v.detach().to(device=p.device, dtype=torch.float32, copy=True)
+
+
+def _require_fp32(opt_name: str, tensors) -> None:
+    for t in tensors:
+        if t is not None and t.dtype is not torch.float32:
+            raise RuntimeError(
+                f"{opt_name}: optimizer state must be float32 for the HIP kernels, got {t.dtype}. "
+                "State is kept in fp32 for every parameter dtype; something cast it "
+                "(torch's Optimizer.load_state_dict does, use this class's own)."
+            )
+
+
 class FusedAdam(torch.optim.Optimizer):
     _ADAM_CHUNK = 4096  # elements per block; must match kAdamChunk in the HIP kernel
 
@@ -34,6 +61,47 @@ class FusedAdam(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self._zeroes_grads_in_kernel = False
         self._mt_cache = {}
+        # host mirror of each group's device step counter: id(group) -> value
+        # the counter holds after the last launch issued from here
+        self._step_host = {}
+
+    def load_state_dict(self, state_dict) -> None:
+        super().load_state_dict(state_dict)
+        _reinstall_fp32_state(self, state_dict)
+        # the groups are new dicts and the state tensors new storage
+        self._mt_cache = {}
+        self._step_host = {}
+
+    def _device_step(self, group, params, step: int) -> Tensor:
+        """The group's device-side step counter (bias correction reads it in
+        the kernel, so a captured step replays with advancing counts).  It is
+        stored as ``step_t`` in the state of the first parameter that had
+        state when it was created, never in an uninitialised state dict, and
+        is found again by scanning the group, so a parameter whose gradient
+        is missing cannot disturb it.  Allocated once: the address is stable."""
+        dev = params[0].device
+        state = self.state
+        holder = None
+        for p in group["params"]:
+            if p in state and "step_t" in state[p]:
+                holder = p
+                break
+        if holder is not None and state[holder]["step_t"].device != dev:
+            del state[holder]["step_t"]
+            holder = None
+        key = id(group)
+        if holder is None:
+            step_t = torch.zeros(1, dtype=torch.float32, device=dev)
+            step_t.fill_(float(step - 1))
+            state[params[0]]["step_t"] = step_t
+        else:
+            step_t = state[holder]["step_t"]
+            # every launch from here advances counter and host step together;
+            # they part only when the set of stepping parameters changed
+            if self._step_host.get(key, step - 1) != step - 1:
+                step_t.fill_(float(step - 1))
+        self._step_host[key] = step
+        return step_t
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         # on GPU the multi-tensor kernel zeroes each grad in place right after
@@ -100,8 +168,14 @@ class FusedAdam(torch.optim.Optimizer):
             if not params:
                 continue
             beta1, beta2 = group["betas"]
-            # all params in a group share the same step count once created
-            step = self.state[params[0]]["step"]
+            # torch.optim.Adam semantics: each parameter is bias-corrected with
+            # its own step count.  Normally every parameter stepping now shares
+            # one count and the shared-counter paths below apply; a parameter
+            # that joined late (its first gradients were None) sends the group
+            # to the per-parameter path at the bottom
+            steps = [self.state[p]["step"] for p in params]
+            step = steps[0]
+            uniform = all(s == step for s in steps)
             bc1 = 1 - beta1**step
             bc2 = 1 - beta2**step
             def _dense_same_layout(p, g):
@@ -113,44 +187,40 @@ class FusedAdam(torch.optim.Optimizer):
                     and (p.is_contiguous() or p.is_contiguous(memory_format=torch.channels_last))
                 )
 
-            if use_hip(params[0]) and all(_dense_same_layout(p, g) for p, g in zip(params, grads)):
+            if uniform and use_hip(params[0]) and all(_dense_same_layout(p, g) for p, g in zip(params, grads)):
                 # device-side step counter: bias correction is computed in the
                 # kernel from a device scalar so the step is hipGraph-capturable;
                 # chunk table makes the whole group ONE kernel launch
-                st0 = self.state[group["params"][0]]
-                if "step_t" not in st0 or st0["step_t"].device != params[0].device:
-                    st0["step_t"] = torch.zeros(1, dtype=torch.float32, device=params[0].device)
-                    st0["step_t"].fill_(float(step - 1))
+                step_t = self._device_step(group, params, step)
+                _require_fp32("FusedAdam", exp_avgs + exp_avg_sqs + [step_t])
                 ent = self._chunk_table(group, params, grads, exp_avgs, exp_avg_sqs)
                 require_ext().adam_step_mt(
                     ent["ptrs"], ent["sizes"], ent["ctid"], ent["coff"],
-                    st0["step_t"], params[0], True,
+                    step_t, params[0], True,
                     group["lr"], beta1, beta2, group["eps"], group["weight_decay"],
                     True,
                 )
-            elif use_hip(params[0]) and all(
+            elif uniform and use_hip(params[0]) and all(
                 # the dev kernel walks p flat and contiguous()-copies g: both
                 # must be standard-contiguous or the orders diverge
                 p.is_contiguous() and g.is_contiguous() for p, g in zip(params, grads)
             ):
-                st0 = self.state[group["params"][0]]
-                if "step_t" not in st0 or st0["step_t"].device != params[0].device:
-                    st0["step_t"] = torch.zeros(1, dtype=torch.float32, device=params[0].device)
-                    st0["step_t"].fill_(float(step - 1))
+                step_t = self._device_step(group, params, step)
+                _require_fp32("FusedAdam", exp_avgs + exp_avg_sqs + [step_t])
                 all_groups_zeroed_in_kernel = False
                 require_ext().adam_step_dev(
                     params,
                     grads,
                     exp_avgs,
                     exp_avg_sqs,
-                    st0["step_t"],
+                    step_t,
                     group["lr"],
                     beta1,
                     beta2,
                     group["eps"],
                     group["weight_decay"],
                 )
-            elif all(p.dtype == torch.float32 and g.dtype == torch.float32 for p, g in zip(params, grads)):
+            elif uniform and all(p.dtype == torch.float32 and g.dtype == torch.float32 for p, g in zip(params, grads)):
                 # foreach eager path (CPU / non-HIP): one C++ multi-tensor op
                 # per stage instead of a Python loop per parameter — the loop
                 # measured ~3 ms/step on the CPU SAC wall-clock benchmark
@@ -169,14 +239,14 @@ class FusedAdam(torch.optim.Optimizer):
                 torch._foreach_add_(params, upd, alpha=-group["lr"])
             else:
                 all_groups_zeroed_in_kernel = False
-                for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
+                for p, g, m, v, s in zip(params, grads, exp_avgs, exp_avg_sqs, steps):
                     gf = g.float()
                     if group["weight_decay"] != 0:
                         gf = gf.add(p.float(), alpha=group["weight_decay"])
                     m.mul_(beta1).add_(gf, alpha=1 - beta1)
                     v.mul_(beta2).addcmul_(gf, gf, value=1 - beta2)
-                    denom = (v / bc2).sqrt_().add_(group["eps"])
-                    upd = (m / bc1) / denom
+                    denom = (v / (1 - beta2**s)).sqrt_().add_(group["eps"])
+                    upd = (m / (1 - beta1**s)) / denom
                     p.add_((-group["lr"] * upd).to(p.dtype))
         self._zeroes_grads_in_kernel = all_groups_zeroed_in_kernel
         return loss
@@ -241,6 +311,11 @@ class RMSpropTF(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self._mt_cache = {}
 
+    def load_state_dict(self, state_dict) -> None:
+        super().load_state_dict(state_dict)
+        _reinstall_fp32_state(self, state_dict)
+        self._mt_cache = {}
+
     def _chunk_table(self, group, params, grads, sqs, mbs, gas):
         dev = params[0].device
         ptr_sig = [p.data_ptr() for p in params] + [g.data_ptr() for g in grads]
@@ -278,7 +353,12 @@ class RMSpropTF(torch.optim.Optimizer):
             # FusedAdam)
             mt = [p for p in group["params"] if p.grad is not None]
             if mt and use_hip(mt[0]) and all(
-                p.dtype == mt[0].dtype and p.is_contiguous() and p.grad.is_contiguous() for p in mt
+                # elementwise: p/g/state only need to share one dense layout
+                # (state is *_like(p)), so channels_last conv weights qualify
+                p.dtype == mt[0].dtype
+                and p.grad.stride() == p.stride()
+                and (p.is_contiguous() or p.is_contiguous(memory_format=torch.channels_last))
+                for p in mt
             ):
                 sqs, mbs, gas = [], [], []
                 for p in mt:
@@ -292,6 +372,7 @@ class RMSpropTF(torch.optim.Optimizer):
                     sqs.append(state["square_avg"])
                     mbs.append(state.get("momentum_buffer"))
                     gas.append(state.get("grad_avg"))
+                _require_fp32("RMSpropTF", sqs + mbs + gas)
                 ent = self._chunk_table(group, mt, [p.grad for p in mt], sqs, mbs, gas)
                 require_ext().rmsprop_step_mt(
                     ent["ptrs"], ent["sizes"], ent["ctid"], ent["coff"], mt[0],

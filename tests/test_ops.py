@@ -275,6 +275,105 @@ def test_fused_adam_zero_grad_unlatches_on_fallback():
     assert p.grad is not None and p.grad.abs().sum().item() == 0.0
 
 
+def _make_opt(kind, params):
+    from sheeprl_amd.optim import FusedAdam, RMSpropTF
+
+    if kind == "adam":
+        return FusedAdam(params, lr=1e-2, weight_decay=1e-2)
+    return RMSpropTF(params, lr=1e-2, momentum=0.9, centered=True)
+
+
+def _tensor_state(opt):
+    """[(param index, key, tensor)] for every tensor in the optimizer state."""
+    out = []
+    params = [p for g in opt.param_groups for p in g["params"]]
+    for i, p in enumerate(params):
+        for k, v in opt.state[p].items():
+            if isinstance(v, torch.Tensor):
+                out.append((i, k, v))
+    return out
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("kind", ["adam", "rmsprop_tf"])
+def test_optimizer_state_dict_round_trip_keeps_fp32_state(kind, dtype):
+    """state_dict() -> load_state_dict() must hand back the fp32 master state
+    bit for bit.  torch's Optimizer.load_state_dict casts tensor state to the
+    parameter dtype, which for bf16 parameters rounds the moments and halves
+    the buffers the HIP kernels address as float*."""
+    torch.manual_seed(11)
+    shapes = [(5,), (3, 4), (7,)]
+    ps = [torch.nn.Parameter(torch.randn(s).to(dtype)) for s in shapes]
+    opt = _make_opt(kind, ps)
+    for _ in range(3):
+        for p in ps:
+            p.grad = (torch.randn(p.shape) * 3 + 1).to(dtype)
+        opt.step()
+    sd = opt.state_dict()
+    saved = {(i, k): v.clone() for i, k, v in _tensor_state(opt)}
+    assert saved, "optimizer holds no tensor state"
+
+    ps2 = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+    opt2 = _make_opt(kind, ps2)
+    opt2.load_state_dict(sd)
+    loaded = {(i, k): v for i, k, v in _tensor_state(opt2)}
+    assert loaded.keys() == saved.keys()
+    for key, v in loaded.items():
+        assert v.dtype == torch.float32, (key, v.dtype)
+        assert v.device == ps2[key[0]].device
+        assert torch.equal(v, saved[key]), key
+    assert opt2._mt_cache == {}
+
+    for p, p2 in zip(ps, ps2):
+        g = (torch.randn(p.shape) * 3 + 1).to(dtype)
+        p.grad = g.clone()
+        p2.grad = g.clone()
+    opt.step()
+    opt2.step()
+    for p, p2 in zip(ps, ps2):
+        assert torch.equal(p, p2)
+    for (i, k, v), (_, _, v2) in zip(_tensor_state(opt), _tensor_state(opt2)):
+        assert v2.dtype == torch.float32 and torch.equal(v, v2), (i, k)
+
+
+@pytest.mark.parametrize("late", [0, 1])
+def test_fused_adam_late_parameter_matches_torch_adam(late):
+    """A parameter whose gradient is None on step 1 joins on step 2: no
+    exception, and every parameter is bias-corrected with its own step count
+    as in torch.optim.Adam (float64 reference)."""
+    from sheeprl_amd.optim import FusedAdam
+
+    torch.manual_seed(12)
+    ps = [torch.nn.Parameter(torch.randn(n)) for n in (6, 9, 4)]
+    refs = [torch.nn.Parameter(p.detach().double().clone()) for p in ps]
+    opt = FusedAdam(ps, lr=1e-2)
+    ref = torch.optim.Adam(refs, lr=1e-2)
+    for step in range(1, 5):
+        for i, (p, r) in enumerate(zip(ps, refs)):
+            if step == 1 and i == late:
+                p.grad = None
+                r.grad = None
+                continue
+            g = torch.randn(p.shape)
+            p.grad = g.clone()
+            r.grad = g.double()
+        opt.step()
+        ref.step()
+        for i, (p, r) in enumerate(zip(ps, refs)):
+            assert torch.allclose(p.detach().double(), r.detach(), atol=1e-6), (step, i)
+
+
+def test_optimizer_state_dtype_guard():
+    """The check in front of the HIP launches: fp32 (and absent) state passes,
+    anything else raises."""
+    from sheeprl_amd.optim.fused import _require_fp32
+
+    _require_fp32("FusedAdam", [torch.zeros(3), None])
+    for dt in (torch.bfloat16, torch.float16, torch.float64):
+        with pytest.raises(RuntimeError, match="float32"):
+            _require_fp32("FusedAdam", [torch.zeros(3), torch.zeros(3, dtype=dt)])
+
+
 def test_ppo_value_loss_clipped_half_factor():
     """Clipped value loss carries the reference's 0.5 factor
     (sheeprl/algos/ppo/loss.py:61)."""
