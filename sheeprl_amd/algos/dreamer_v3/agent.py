@@ -506,6 +506,18 @@ class Actor(nn.Module):
             actions_list.append(onehot)
         return tuple(actions_list), tuple(dists)
 
+    def policy_log_probs(self, state: Tensor) -> Tensor:
+        """Normalized (unimix) log-probs of every discrete head, concatenated
+        to [..., sum(actions_dim)] in head order — what the fused REINFORCE
+        loss consumes.  One ragged kernel instead of a ``categorical_st`` per
+        head; no sampling, so no random numbers are drawn."""
+        if self.is_continuous:
+            raise ValueError("policy_log_probs is defined for discrete actors only")
+        out = self.model(state)
+        logits = torch.cat([head(out) for head in self.mlp_heads], dim=-1)
+        m, _ = ops.categorical_st_ragged(logits, self.actions_dim, self._unimix, sample=False)
+        return m
+
 
 class MinedojoActor(Actor):
     """Action-masked actor for MineDojo (reference dreamer_v3/agent.py:848-933).

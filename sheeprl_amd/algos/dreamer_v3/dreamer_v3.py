@@ -273,11 +273,12 @@ def train(
             actions = torch.cat(actor(imagined_latent_state.detach())[0], dim=-1).to(dtype)
             imagined_actions[i] = actions
 
-    # fast behaviour-loss path (discrete single-head on HIP): for a REINFORCE
-    # actor nothing backpropagates through the imagined values/returns, so the
-    # value/reward/continue heads run inference-only with fused twohot means,
-    # and each loss is ONE kernel per direction instead of the autograd chain
-    fast_losses = use_fast_imagine and len(actions_dim) == 1
+    # fast behaviour-loss path (discrete heads on HIP, one or MultiDiscrete):
+    # for a REINFORCE actor nothing backpropagates through the imagined
+    # values/returns, so the value/reward/continue heads run inference-only
+    # with fused twohot means, and each loss is ONE kernel per direction
+    # instead of the autograd chain
+    fast_losses = use_fast_imagine
     if fast_losses:
         with torch.no_grad():
             # the three trajectory sweeps are independent — fork them
@@ -306,11 +307,17 @@ def train(
         with br_beh.fork():
             # actor loss (advantage offsets cancel: (λ-off)/s - (v-off)/s = (λ-v)/s)
             actor_optimizer.zero_grad(set_to_none=True)
-            policies = actor(imagined_trajectories.detach())[1]
+            if len(actions_dim) == 1:
+                policy_m = actor(imagined_trajectories.detach())[1][0].logits
+            else:
+                # the loss's sum_a m*act and -sum_a e^m m are additive over
+                # heads: the concatenated per-head log-probs and one-hots give
+                # the summed per-head log_prob and entropy of the module path
+                policy_m = actor.policy_log_probs(imagined_trajectories.detach())
             with torch.no_grad():
                 advantage = (lambda_values - predicted_values[:-1]) / invscale
             policy_loss = ops.reinforce_loss(
-                policies[0].logits, imagined_actions, advantage, discount[:-1], cfg.algo.actor.ent_coef
+                policy_m, imagined_actions, advantage, discount[:-1], cfg.algo.actor.ent_coef
             )
             runtime.backward(policy_loss)
             actor_grads = None

@@ -13,6 +13,12 @@ Semantics are identical to the module loop (same kernels, same philox
 consumption ORDER differs only in that the per-step ``torch.rand`` calls are
 replaced by two batched draws — any iid uniforms are equivalent here);
 validated against the module loop in tests/test_gpu_kernels.py.
+
+MultiDiscrete action spaces (several discrete heads) ride the same rollout:
+the head weights are concatenated once per call, so a step is still one head
+GEMM plus one sampler launch — the ragged ``cat_st_ragged_fwd_o``, which is
+bit-identical per head to the single-head kernel
+(tests/test_gpu_ragged_actions.py).
 """
 
 from __future__ import annotations
@@ -23,14 +29,17 @@ import torch
 from torch import Tensor
 
 from sheeprl_amd.ops._ext import require_ext
+from sheeprl_amd.ops.categorical import MAX_RAGGED_HEADS
 
 
 def imagine_applicable(rssm: Any, actor: Any) -> bool:
-    """Fast rollout needs the canonical DV3 discrete setup: single discrete
-    actor head, LN+SiLU dense blocks without bias everywhere, and the
-    standard transition-model shape."""
+    """Fast rollout needs the canonical DV3 discrete setup: discrete actor
+    heads (one, or several for MultiDiscrete spaces), LN+SiLU dense blocks
+    without bias everywhere, and the standard transition-model shape."""
     try:
-        if actor.is_continuous or len(actor.mlp_heads) != 1:
+        # the ragged sampler takes at most MAX_RAGGED_HEADS heads per launch;
+        # actors beyond that keep the module loop
+        if actor.is_continuous or not 1 <= len(actor.mlp_heads) <= MAX_RAGGED_HEADS:
             return False
         trans = rssm.transition_model.model
         mlp_block = rssm.recurrent_model.mlp
@@ -68,7 +77,15 @@ def imagine_rollout(
     mlp_block = rssm.recurrent_model.mlp
     gru = rssm.recurrent_model.rnn
     trans = rssm.transition_model.model
-    head = actor.mlp_heads[0]
+    heads = list(actor.mlp_heads)
+    head_sizes = [int(h.out_features) for h in heads]
+    if len(heads) == 1:
+        head_w, head_b = heads[0].weight, heads[0].bias
+    else:
+        # MultiDiscrete: one concatenated head GEMM + one ragged sampler launch
+        # per step, whatever the head count (built once, outside the step loop)
+        head_w = torch.cat([h.weight for h in heads], 0)
+        head_b = torch.cat([h.bias for h in heads], 0)
     actor_blocks = list(actor.model.model)
     eps = 1e-3
     unimix = float(rssm.unimix)
@@ -80,7 +97,7 @@ def imagine_rollout(
     B, SK = z0.shape
     H = h0.shape[-1]
     S = SK // K
-    A = head.out_features
+    A = sum(head_sizes)
     DU = mlp_block.linear.out_features
     P = trans[0].linear.out_features
     HZ = horizon
@@ -120,9 +137,13 @@ def imagine_rollout(
             torch.mm(x, blk.linear.weight.t(), out=pre)
             ext.ln_act_fwd_o(pre, blk.ln_weight, blk.ln_bias, blk.ln_eps, True, hid, mr[0], mr[1])
             x = hid
-        torch.addmm(head.bias, x, head.weight.t(), out=alogits)
+        torch.addmm(head_b, x, head_w.t(), out=alogits)
         # the sampled action ALSO lands in the next step's GEMM input slice
-        ext.cat_st_fwd_o(alogits, urand_a[i], a_unimix, am_tmp, acts[i], as_tmp, xs[:, SK:])
+        if len(heads) == 1:
+            ext.cat_st_fwd_o(alogits, urand_a[i], a_unimix, am_tmp, acts[i], as_tmp, xs[:, SK:])
+        else:
+            ext.cat_st_ragged_fwd_o(alogits, urand_a[i], head_sizes, a_unimix, True, am_tmp, as_tmp, acts[i],
+                                    xs[:, SK:])
 
     # the producing kernels write every next-step input in place (second /
     # third strided outputs), so the per-step assembly copies are gone; only

@@ -50,6 +50,15 @@ AGGREGATOR_KEYS = {
 MODELS_TO_REGISTER = {"world_model", "ensembles", "actor_task", "critic_task", "target_critic_task", "actor_exploration"}
 
 
+def _policy_log_probs(actor, latent_states):
+    """Normalized log-probs for ``ops.reinforce_loss``: the single head's, or
+    (MultiDiscrete) every head's concatenated — the loss is additive over
+    heads."""
+    if len(actor.mlp_heads) == 1:
+        return actor(latent_states)[1][0].logits
+    return actor.policy_log_probs(latent_states)
+
+
 def train(
     runtime: Runtime,
     world_model,
@@ -158,11 +167,11 @@ def train(
     flat = batch_size * sequence_length
     # DV3 fast path (launch-lean no-grad rollout + fused REINFORCE/critic
     # losses): valid because nothing backpropagates through the imagined
-    # rollout for a discrete single-head actor (every consumer detaches)
+    # rollout for a discrete actor, one head or MultiDiscrete (every consumer
+    # detaches)
     use_fast = (
         cfg.algo.get("fused_imagination", True)
         and not is_continuous
-        and len(actions_dim) == 1
         and device.type == "cuda"
         and imagine_applicable(world_model.rssm, actor_exploration)
         and imagine_applicable(world_model.rssm, actor_task)
@@ -247,12 +256,13 @@ def train(
         discount = torch.cumprod(continues * cfg.algo.gamma, dim=0) / cfg.algo.gamma
 
     actor_exploration_optimizer.zero_grad(set_to_none=True)
-    policies = actor_exploration(imagined_trajectories.detach())[1]
     if use_fast:
         policy_loss_expl = ops.reinforce_loss(
-            policies[0].logits, imagined_actions, advantage, discount[:-1], cfg.algo.actor.ent_coef
+            _policy_log_probs(actor_exploration, imagined_trajectories.detach()),
+            imagined_actions, advantage, discount[:-1], cfg.algo.actor.ent_coef,
         )
     else:
+        policies = actor_exploration(imagined_trajectories.detach())[1]
         if is_continuous:
             objective = advantage
         else:
@@ -323,12 +333,12 @@ def train(
             discount = torch.cumprod(continues * cfg.algo.gamma, dim=0) / cfg.algo.gamma
 
         actor_task_optimizer.zero_grad(set_to_none=True)
-        policies = actor_task(imagined_trajectories.detach())[1]
+        policy_m = _policy_log_probs(actor_task, imagined_trajectories.detach())
         offset, invscale = moments_task(lambda_values, runtime)
         with torch.no_grad():
             advantage = (lambda_values - predicted_values[:-1]) / invscale
         policy_loss_task = ops.reinforce_loss(
-            policies[0].logits, imagined_actions, advantage, discount[:-1], cfg.algo.actor.ent_coef
+            policy_m, imagined_actions, advantage, discount[:-1], cfg.algo.actor.ent_coef
         )
     else:
         imagined_prior = posteriors.detach().reshape(1, -1, stoch_state_size)

@@ -2361,6 +2361,278 @@ void cat_st_bwd_o(const torch::Tensor& gm, const torch::Tensor& gon, const c10::
 }
 
 // ---------------------------------------------------------------------------
+// ragged unimix-categorical straight-through head (MultiDiscrete actors)
+// rows of A = sum_h K_h logits, head h in columns [off_h, off_h + K_h): the
+// per-head math, loop order, reductions and tie-break are cat_st_fwd_kernel's
+// verbatim (one wave per (row, head)), so every output is bit-identical to
+// the per-head kernel run on that head's column slice.  The head table rides
+// in the kernel arguments (no device table, no H2D copy: capture-safe).
+// ---------------------------------------------------------------------------
+
+constexpr int kMaxRaggedHeads = 8;
+
+struct RaggedHeads {
+  int n;
+  int off[kMaxRaggedHeads];
+  int size[kMaxRaggedHeads];
+};
+
+// select chain, not heads.off[h]: a runtime index into a by-value table may
+// be lowered through a private copy (scratch)
+__device__ __forceinline__ void ragged_head(const RaggedHeads& heads, int h, int& off, int& K) {
+  off = heads.off[0];
+  K = heads.size[0];
+#pragma unroll
+  for (int i = 1; i < kMaxRaggedHeads; ++i) {
+    if (h == i) {
+      off = heads.off[i];
+      K = heads.size[i];
+    }
+  }
+}
+
+template <typename T, bool SAMPLE>
+__global__ void __launch_bounds__(256)
+    cat_st_ragged_fwd_kernel(const T* __restrict__ raw, const float* __restrict__ urand,
+                             float* __restrict__ m_out, T* __restrict__ onehot, float* __restrict__ s_out,
+                             long nrows, int A, RaggedHeads heads, float unimix, long ohs,
+                             T* __restrict__ onehot2, long oh2s) {
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const long row = wave / heads.n;
+  if (row >= nrows) return;
+  int hoff, K;
+  ragged_head(heads, (int)(wave % heads.n), hoff, K);
+  const T* L = raw + row * (long)A + hoff;
+  float* mr = m_out + row * (long)A + hoff;
+  float* sr = s_out + row * (long)A + hoff;
+  const float* ur = SAMPLE ? urand + row * (long)A + hoff : nullptr;
+  T* oh = onehot ? onehot + row * ohs + hoff : nullptr;
+  T* oh2 = onehot2 ? onehot2 + row * oh2s + hoff : nullptr;
+  // head max
+  float lmax = -1e30f;
+  for (int j = lane; j < K; j += 64) lmax = fmaxf(lmax, ld(L, j));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
+  // exp + sum
+  float lsum = 0.f;
+  for (int j = lane; j < K; j += 64) lsum += texp<T>(ld(L, j) - lmax);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
+  const float inv = 1.f / lsum;
+  // p, m, gumbel-argmax
+  float best = -1e30f;
+  int best_j = 0;
+  for (int j = lane; j < K; j += 64) {
+    float s = texp<T>(ld(L, j) - lmax) * inv;
+    float p = (1.f - unimix) * s + unimix / K;
+    float m = tlog<T>(p);
+    sr[j] = s;
+    mr[j] = m;
+    float score = m;
+    if (SAMPLE) {
+      float u = ur[j];
+      float t = fmaxf(-tlog<T>(fmaxf(u, 1e-20f)), 1e-20f);
+      score += -tlog<T>(t);  // Gumbel(0,1) noise
+    }
+    if (score > best) {
+      best = score;
+      best_j = j;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    float ob = __shfl_xor(best, off, 64);
+    int oj = __shfl_xor(best_j, off, 64);
+    if (ob > best || (ob == best && oj < best_j)) {
+      best = ob;
+      best_j = oj;
+    }
+  }
+  if (!oh && !oh2) return;  // log-probs only (sample=false, no destination)
+  for (int j = lane; j < K; j += 64) {
+    const float z = j == best_j ? 1.f : 0.f;
+    if (oh) st(oh, j, z);
+    if (oh2) st(oh2, j, z);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+    cat_st_ragged_bwd_kernel(const float* __restrict__ gm, const T* __restrict__ gon,
+                             const float* __restrict__ s_saved, T* __restrict__ graw, long nrows, int A,
+                             RaggedHeads heads, float unimix) {
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const long row = wave / heads.n;
+  if (row >= nrows) return;
+  int hoff, K;
+  ragged_head(heads, (int)(wave % heads.n), hoff, K);
+  const float* gmr = gm + row * (long)A + hoff;
+  const T* gor = gon ? gon + row * (long)A + hoff : nullptr;
+  const float* sr = s_saved + row * (long)A + hoff;
+  T* gr = graw + row * (long)A + hoff;
+  float acc = 0.f;
+  for (int j = lane; j < K; j += 64) {
+    float sj = sr[j];
+    float pj = (1.f - unimix) * sj + unimix / K;
+    float t = gmr[j] / pj + (gor ? ld(gor, j) : 0.f);
+    acc += t * sj;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  for (int j = lane; j < K; j += 64) {
+    float sj = sr[j];
+    float pj = (1.f - unimix) * sj + unimix / K;
+    float t = gmr[j] / pj + (gor ? ld(gor, j) : 0.f);
+    st(gr, j, (1.f - unimix) * sj * (t - acc));
+  }
+}
+
+static RaggedHeads ragged_heads(const std::vector<int64_t>& sizes, int64_t A, const char* who) {
+  TORCH_CHECK(!sizes.empty() && (int)sizes.size() <= kMaxRaggedHeads, who, ": between 1 and ", kMaxRaggedHeads,
+              " heads supported, got ", sizes.size());
+  RaggedHeads heads;
+  heads.n = (int)sizes.size();
+  int64_t off = 0;
+  for (int i = 0; i < kMaxRaggedHeads; ++i) {
+    const int64_t k = i < heads.n ? sizes[i] : 0;
+    TORCH_CHECK(i >= heads.n || k >= 1, who, ": every head size must be >= 1");
+    heads.off[i] = (int)off;
+    heads.size[i] = (int)k;
+    off += k;
+  }
+  TORCH_CHECK(off == A, who, ": sum(sizes) = ", off, " does not match the last dimension ", A);
+  return heads;
+}
+
+// row stride of a one-hot destination: contiguous [.., A] or a 2-D
+// row-strided [rows, A] slice of a wider buffer
+static long ragged_onehot_stride(const torch::Tensor& oh, const torch::Tensor& raw, long nrows, int A,
+                                 const char* who) {
+  TORCH_CHECK(oh.is_cuda() && oh.scalar_type() == raw.scalar_type(), who, ": onehot must be a CUDA tensor of raw's dtype");
+  TORCH_CHECK(oh.numel() == nrows * (long)A && oh.size(-1) == A, who, ": onehot shape does not match raw");
+  if (oh.is_contiguous()) return (long)A;
+  TORCH_CHECK(oh.dim() == 2 && oh.stride(1) == 1 && oh.stride(0) >= A, who,
+              ": onehot must be contiguous or a row-strided 2-D slice");
+  return (long)oh.stride(0);
+}
+
+template <typename T>
+static void cat_st_ragged_launch(const torch::Tensor& raw, const float* up, float* m, T* oh, float* s, long nrows,
+                                 int A, const RaggedHeads& heads, double unimix, long ohs, T* oh2, long oh2s,
+                                 bool sample) {
+  const long waves = nrows * heads.n;
+  const int waves_per_block = kBlock / 64;
+  const int blocks = (int)((waves + waves_per_block - 1) / waves_per_block);
+  if (blocks == 0) return;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (sample)
+    hipLaunchKernelGGL((cat_st_ragged_fwd_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
+                       (const T*)raw.data_ptr(), up, m, oh, s, nrows, A, heads, (float)unimix, ohs, oh2, oh2s);
+  else
+    hipLaunchKernelGGL((cat_st_ragged_fwd_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
+                       (const T*)raw.data_ptr(), up, m, oh, s, nrows, A, heads, (float)unimix, ohs, oh2, oh2s);
+}
+
+static const float* ragged_urand(const c10::optional<torch::Tensor>& urand, const torch::Tensor& raw, bool sample,
+                                 const char* who) {
+  if (!sample) return nullptr;
+  TORCH_CHECK(urand.has_value(), who, ": sample=true needs urand");
+  const torch::Tensor& u = *urand;
+  CHECK_IN(u);
+  TORCH_CHECK(u.scalar_type() == at::kFloat && u.numel() == raw.numel() && u.size(-1) == raw.size(-1), who,
+              ": urand must be fp32 with raw's shape");
+  return u.data_ptr<float>();
+}
+
+std::vector<torch::Tensor> cat_st_ragged_fwd(const torch::Tensor& raw, const c10::optional<torch::Tensor>& urand,
+                                             std::vector<int64_t> sizes, double unimix, bool sample) {
+  CHECK_IN(raw);
+  TORCH_CHECK(raw.dim() >= 1, "cat_st_ragged_fwd: raw needs a last dimension");
+  const int A = (int)raw.size(-1);
+  const RaggedHeads heads = ragged_heads(sizes, A, "cat_st_ragged_fwd");
+  const long nrows = raw.numel() / A;
+  const float* up = ragged_urand(urand, raw, sample, "cat_st_ragged_fwd");
+  auto m = torch::empty(raw.sizes(), raw.options().dtype(at::kFloat));
+  auto s = torch::empty(raw.sizes(), raw.options().dtype(at::kFloat));
+  auto onehot = torch::empty_like(raw);
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_ragged_fwd", [&] {
+    using T = scalar_t;
+    cat_st_ragged_launch<T>(raw, up, m.data_ptr<float>(), (T*)onehot.data_ptr(), s.data_ptr<float>(), nrows, A,
+                            heads, unimix, (long)A, (T*)nullptr, 0L, sample);
+  });
+  return {m, onehot, s};
+}
+
+// Out-variant for the fast imagination rollout: m/s are caller-provided fp32
+// buffers; the one-hot goes to up to two destinations (contiguous or
+// row-strided slices), or nowhere when only the log-probs are wanted.
+void cat_st_ragged_fwd_o(const torch::Tensor& raw, const c10::optional<torch::Tensor>& urand,
+                         std::vector<int64_t> sizes, double unimix, bool sample, torch::Tensor m,
+                         torch::Tensor s, const c10::optional<torch::Tensor>& onehot = c10::nullopt,
+                         const c10::optional<torch::Tensor>& onehot2 = c10::nullopt) {
+  CHECK_IN(raw);
+  CHECK_IN(m);
+  CHECK_IN(s);
+  TORCH_CHECK(raw.dim() >= 1, "cat_st_ragged_fwd_o: raw needs a last dimension");
+  const int A = (int)raw.size(-1);
+  const RaggedHeads heads = ragged_heads(sizes, A, "cat_st_ragged_fwd_o");
+  const long nrows = raw.numel() / A;
+  const float* up = ragged_urand(urand, raw, sample, "cat_st_ragged_fwd_o");
+  TORCH_CHECK(m.scalar_type() == at::kFloat && s.scalar_type() == at::kFloat && m.numel() == raw.numel() &&
+                  s.numel() == raw.numel(),
+              "cat_st_ragged_fwd_o: m and s must be fp32 with raw's element count");
+  TORCH_CHECK(!sample || onehot.has_value(), "cat_st_ragged_fwd_o: sample=true needs a onehot destination");
+  TORCH_CHECK(onehot.has_value() || !onehot2.has_value(), "cat_st_ragged_fwd_o: onehot2 without onehot");
+  long ohs = 0, oh2s = 0;
+  if (onehot.has_value()) ohs = ragged_onehot_stride(*onehot, raw, nrows, A, "cat_st_ragged_fwd_o");
+  if (onehot2.has_value()) oh2s = ragged_onehot_stride(*onehot2, raw, nrows, A, "cat_st_ragged_fwd_o");
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_ragged_fwd_o", [&] {
+    using T = scalar_t;
+    T* oh = onehot.has_value() ? (T*)onehot->data_ptr() : nullptr;
+    T* oh2 = onehot2.has_value() ? (T*)onehot2->data_ptr() : nullptr;
+    cat_st_ragged_launch<T>(raw, up, m.data_ptr<float>(), oh, s.data_ptr<float>(), nrows, A, heads, unimix, ohs,
+                            oh2, oh2s, sample);
+  });
+}
+
+torch::Tensor cat_st_ragged_bwd(const torch::Tensor& gm, const c10::optional<torch::Tensor>& gon,
+                                const torch::Tensor& s, std::vector<int64_t> sizes, double unimix,
+                                c10::optional<at::ScalarType> out_dtype = c10::nullopt) {
+  CHECK_IN(gm);
+  CHECK_IN(s);
+  TORCH_CHECK(gm.dim() >= 1, "cat_st_ragged_bwd: gm needs a last dimension");
+  const int A = (int)gm.size(-1);
+  const RaggedHeads heads = ragged_heads(sizes, A, "cat_st_ragged_bwd");
+  const long nrows = gm.numel() / A;
+  TORCH_CHECK(gm.scalar_type() == at::kFloat && s.scalar_type() == at::kFloat && s.numel() == gm.numel(),
+              "cat_st_ragged_bwd: gm and s must be fp32 of the same size");
+  if (gon.has_value()) {
+    const torch::Tensor& g = *gon;
+    CHECK_IN(g);
+    TORCH_CHECK(g.numel() == gm.numel(), "cat_st_ragged_bwd: gon size does not match gm");
+    TORCH_CHECK(!out_dtype.has_value() || *out_dtype == g.scalar_type(),
+                "cat_st_ragged_bwd: out_dtype must equal gon's dtype");
+  }
+  const at::ScalarType dt = gon.has_value() ? gon->scalar_type() : out_dtype.value_or(at::kFloat);
+  auto graw = torch::empty(gm.sizes(), gm.options().dtype(dt));
+  const long waves = nrows * heads.n;
+  const int waves_per_block = kBlock / 64;
+  const int blocks = (int)((waves + waves_per_block - 1) / waves_per_block);
+  if (blocks == 0) return graw;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, dt, "cat_st_ragged_bwd", [&] {
+    using T = scalar_t;
+    const T* gp = gon.has_value() ? (const T*)gon->data_ptr() : nullptr;
+    hipLaunchKernelGGL((cat_st_ragged_bwd_kernel<T>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
+                       gm.data_ptr<float>(), gp, s.data_ptr<float>(), (T*)graw.data_ptr(), nrows, A, heads,
+                       (float)unimix);
+  });
+  return graw;
+}
+
+// ---------------------------------------------------------------------------
 // masked lerp (episode-reset masking in the RSSM scan):
 //   y[b, j] = (1 - f[b]) * x[b, j] + f[b] * init[b, j]      (init optional)
 // backward: gx = (1-f) * g ; ginit = f * g
@@ -6610,6 +6882,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cat_st_fwd_o", &cat_st_fwd_o, py::arg("raw"), py::arg("urand"), py::arg("unimix"),
         py::arg("m"), py::arg("onehot"), py::arg("s"), py::arg("onehot2") = c10::nullopt);
   m.def("cat_st_bwd_o", &cat_st_bwd_o);
+  m.attr("MAX_RAGGED_HEADS") = kMaxRaggedHeads;
+  m.def("cat_st_ragged_fwd", &cat_st_ragged_fwd, py::arg("raw"), py::arg("urand"), py::arg("sizes"),
+        py::arg("unimix"), py::arg("sample"));
+  m.def("cat_st_ragged_fwd_o", &cat_st_ragged_fwd_o, py::arg("raw"), py::arg("urand"), py::arg("sizes"),
+        py::arg("unimix"), py::arg("sample"), py::arg("m"), py::arg("s"), py::arg("onehot") = c10::nullopt,
+        py::arg("onehot2") = c10::nullopt);
+  m.def("cat_st_ragged_bwd", &cat_st_ragged_bwd, py::arg("gm"), py::arg("gon"), py::arg("s"), py::arg("sizes"),
+        py::arg("unimix"), py::arg("out_dtype") = c10::nullopt);
   m.def("ema_update", &ema_update);
   m.def("obs_norm", &obs_norm);
   m.def("chlast_bias_sum", &chlast_bias_sum);

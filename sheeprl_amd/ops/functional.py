@@ -279,10 +279,12 @@ def twohot_mean(logits: Tensor, low: float = -20.0, high: float = 20.0) -> Tenso
 
 
 class _ReinforceLoss(torch.autograd.Function):
-    """Discrete single-head DV3 actor loss:
+    """Discrete DV3 actor loss:
     -(1/(HZ*F)) sum disc * (logp(a) * adv + ent_coef * entropy), with
     normalized log-probs ``m`` [HZ+1, F, A] (the t=HZ row is unused, matching
-    the reference's [:-1] slicing)."""
+    the reference's [:-1] slicing).  Both sums are additive over heads, so a
+    MultiDiscrete actor passes its per-head log-probs and one-hots
+    concatenated along A."""
 
     @staticmethod
     def forward(ctx, m: Tensor, act: Tensor, adv: Tensor, disc: Tensor, ent_coef: float) -> Tensor:
