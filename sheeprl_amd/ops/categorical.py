@@ -20,25 +20,38 @@ from torch import Tensor
 from sheeprl_amd.ops._ext import require_ext, use_hip
 
 
+def _ref_fwd(raw: Tensor, unimix: float, u: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """CPU reference for one head [..., K]: (m, s, one-hot); ``u`` (uniforms of
+    raw's shape) drives the Gumbel-max sample, ``None`` takes argmax(m)."""
+    K = raw.shape[-1]
+    s = torch.softmax(raw.float(), dim=-1)
+    m = torch.log((1.0 - unimix) * s + unimix / K)
+    score = m
+    if u is not None:
+        score = m - torch.log(torch.clamp(-torch.log(u.clamp_min(1e-20)), min=1e-20))
+    return m, s, torch.nn.functional.one_hot(score.argmax(-1), K).to(raw.dtype)
+
+
+def _ref_bwd(gm: Tensor, gon: Optional[Tensor], s: Tensor, unimix: float) -> Tensor:
+    """CPU reference for one head: fp32 grad wrt the raw logits."""
+    p = (1.0 - unimix) * s + unimix / s.shape[-1]
+    t = gm.float() / p
+    if gon is not None:
+        t = t + gon.float()
+    acc = (t * s).sum(-1, keepdim=True)
+    return (1.0 - unimix) * s * (t - acc)
+
+
 class _CategoricalST(torch.autograd.Function):
     @staticmethod
     def forward(ctx, raw: Tensor, unimix: float, sample: bool) -> Tuple[Tensor, Tensor]:
-        K = raw.shape[-1]
         if use_hip(raw):
             rawc = raw.contiguous()
             u = torch.rand(rawc.shape, dtype=torch.float32, device=raw.device) if sample else None
             m, onehot, s = require_ext().cat_st_fwd(rawc, u, float(unimix), bool(sample))
         else:
-            s = torch.softmax(raw.float(), dim=-1)
-            p = (1.0 - unimix) * s + unimix / K
-            m = torch.log(p)
-            if sample:
-                u = torch.rand_like(m)
-                g = -torch.log(torch.clamp(-torch.log(u.clamp_min(1e-20)), min=1e-20))
-                idx = (m + g).argmax(-1)
-            else:
-                idx = m.argmax(-1)
-            onehot = torch.nn.functional.one_hot(idx, K).to(raw.dtype)
+            u = torch.rand(raw.shape, dtype=torch.float32, device=raw.device) if sample else None
+            m, s, onehot = _ref_fwd(raw, unimix, u)
         ctx.save_for_backward(s)
         ctx.unimix = unimix
         ctx.raw_dtype = raw.dtype
@@ -51,11 +64,7 @@ class _CategoricalST(torch.autograd.Function):
         if use_hip(s):
             graw = require_ext().cat_st_bwd(gm.contiguous(), gon.contiguous().to(ctx.raw_dtype), s, float(unimix))
         else:
-            K = s.shape[-1]
-            p = (1.0 - unimix) * s + unimix / K
-            t = gm.float() / p + gon.float()
-            acc = (t * s).sum(-1, keepdim=True)
-            graw = ((1.0 - unimix) * s * (t - acc)).to(ctx.raw_dtype)
+            graw = _ref_bwd(gm, gon, s, unimix).to(ctx.raw_dtype)
         return graw, None, None
 
 
@@ -112,25 +121,14 @@ class _CategoricalSTRagged(torch.autograd.Function):
                 ]
                 m, onehot, s = (torch.cat([p[i] for p in parts], -1) for i in range(3))
         else:
-            ms, ss, ohs = [], [], []
             if sample and urand is None:
                 urand = torch.rand(raw.shape, dtype=torch.float32, device=raw.device)
-            off = 0
+            heads, off = [], 0
             for K in sizes:
-                sh = torch.softmax(raw[..., off : off + K].float(), dim=-1)
-                p = (1.0 - unimix) * sh + unimix / K
-                mh = torch.log(p)
-                if sample:
-                    u = urand[..., off : off + K]
-                    g = -torch.log(torch.clamp(-torch.log(u.clamp_min(1e-20)), min=1e-20))
-                    idx = (mh + g).argmax(-1)
-                else:
-                    idx = mh.argmax(-1)
-                ms.append(mh)
-                ss.append(sh)
-                ohs.append(torch.nn.functional.one_hot(idx, K).to(raw.dtype))
+                u = urand[..., off : off + K] if sample else None
+                heads.append(_ref_fwd(raw[..., off : off + K], unimix, u))
                 off += K
-            m, s, onehot = torch.cat(ms, -1), torch.cat(ss, -1), torch.cat(ohs, -1)
+            m, s, onehot = (torch.cat([h[i] for h in heads], -1) for i in range(3))
         ctx.save_for_backward(s)
         ctx.sizes = tuple(sizes)
         ctx.unimix = unimix
@@ -168,16 +166,10 @@ class _CategoricalSTRagged(torch.autograd.Function):
                     -1,
                 )
         else:
-            gs = []
-            off = 0
+            gs, off = [], 0
             for K in ctx.sizes:
-                sh = s[..., off : off + K]
-                p = (1.0 - unimix) * sh + unimix / K
-                t = gm[..., off : off + K].float() / p
-                if gon is not None:
-                    t = t + gon[..., off : off + K].float()
-                acc = (t * sh).sum(-1, keepdim=True)
-                gs.append((1.0 - unimix) * sh * (t - acc))
+                gon_h = None if gon is None else gon[..., off : off + K]
+                gs.append(_ref_bwd(gm[..., off : off + K], gon_h, s[..., off : off + K], unimix))
                 off += K
             graw = torch.cat(gs, -1).to(ctx.raw_dtype)
         return graw, None, None, None, None

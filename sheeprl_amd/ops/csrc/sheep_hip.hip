@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <type_traits>
 #include <vector>
 
 #define CHECK_IN(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous CUDA tensor")
@@ -119,6 +120,129 @@ __device__ __forceinline__ void st(T* p, long i, float v) {
 template <>
 __device__ __forceinline__ void st<__hip_bfloat16>(__hip_bfloat16* p, long i, float v) {
   p[i] = __float2bfloat16(v);
+}
+
+// ---------------------------------------------------------------------------
+// unimix categorical straight-through cores: the one home of the head's math
+// (mix formula, clamps, sentinels, tie-break, closed-form backward), one core
+// per execution shape.  Every cat_st / g16 / pk / scan2 / scan3 sampler
+// kernel calls these, so kernels of one shape agree bit for bit.
+//   s = softmax(L) ; p = (1-u)*s + u/K ; m = log p
+//   sample = argmax_j(m_j + gumbel_j), lowest index on ties
+//   g_L_j = (1-u) * s_j * (t_j - sum_i t_i * s_i),  t_j = gm_j/p_j + ST grads
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ float cat_st_mix(float s, int K, float unimix) {
+  return (1.f - unimix) * s + unimix / K;
+}
+
+// argmax score of a column: m plus Gumbel(0,1) noise from the uniform u
+// (T = float is the libm instantiation)
+template <typename T>
+__device__ __forceinline__ float cat_st_gumbel(float m, float u) {
+  float t = fmaxf(-tlog<T>(fmaxf(u, 1e-20f)), 1e-20f);
+  return m - tlog<T>(t);
+}
+
+// Wave forward: the 64 lanes of a wave stride over one row of K logits.
+// Writes sr[j] = s and mr[j] = m, returns the wave-uniform sampled index
+// (argmax of m when !SAMPLE; ur is not read then).
+template <typename T, bool SAMPLE>
+__device__ __forceinline__ int cat_st_wave_fwd(const T* L, const float* ur, float* mr, float* sr, int K,
+                                               float unimix, int lane) {
+  float lmax = -1e30f;
+  for (int j = lane; j < K; j += 64) lmax = fmaxf(lmax, ld(L, j));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
+  float lsum = 0.f;
+  for (int j = lane; j < K; j += 64) lsum += texp<T>(ld(L, j) - lmax);
+  lsum = wave_sum(lsum);
+  const float inv = 1.f / lsum;
+  float best = -1e30f;
+  int best_j = 0;
+  for (int j = lane; j < K; j += 64) {
+    float s = texp<T>(ld(L, j) - lmax) * inv;
+    float m = tlog<T>(cat_st_mix(s, K, unimix));
+    sr[j] = s;
+    mr[j] = m;
+    float score = m;
+    if (SAMPLE) score = cat_st_gumbel<T>(m, ur[j]);
+    if (score > best) {
+      best = score;
+      best_j = j;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    float ob = __shfl_xor(best, off, 64);
+    int oj = __shfl_xor(best_j, off, 64);
+    if (ob > best || (ob == best && oj < best_j)) {
+      best = ob;
+      best_j = oj;
+    }
+  }
+  return best_j;
+}
+
+// Wave backward over one row.  add_st(j, a, first) returns t_j given
+// a = gm_j/p_j: the kernel adds its straight-through gradient terms there, in
+// its own order.  It runs once per pass; `first` marks the reduction pass.
+template <typename T, typename AddSt>
+__device__ __forceinline__ void cat_st_wave_bwd(const float* gmr, const float* sr, T* gr, int K, float unimix,
+                                                int lane, AddSt add_st) {
+  float acc = 0.f;
+  for (int j = lane; j < K; j += 64) {
+    float sj = sr[j];
+    float t = add_st(j, gmr[j] / cat_st_mix(sj, K, unimix), true);
+    acc += t * sj;
+  }
+  acc = wave_sum(acc);
+  for (int j = lane; j < K; j += 64) {
+    float sj = sr[j];
+    float t = add_st(j, gmr[j] / cat_st_mix(sj, K, unimix), false);
+    st(gr, j, (1.f - unimix) * sj * (t - acc));
+  }
+}
+
+// Group-serial forward: one thread walks a whole group of KD logits (a GEMM
+// tile row in LDS) and writes m, s and the bf16 one-hot.  libm throughout.
+__device__ __forceinline__ void cat_st_group_fwd(const float* row, const float* ur, float* mr, float* sr,
+                                                 __hip_bfloat16* zr, int KD, float unimix) {
+  float lmax = -1e30f;
+  for (int j = 0; j < KD; ++j) lmax = fmaxf(lmax, row[j]);
+  float lsum = 0.f;
+  for (int j = 0; j < KD; ++j) lsum += expf(row[j] - lmax);
+  const float inv = 1.f / lsum;
+  float best = -1e30f;
+  int best_j = 0;
+  for (int j = 0; j < KD; ++j) {
+    float sv = expf(row[j] - lmax) * inv;
+    float mv = logf(cat_st_mix(sv, KD, unimix));
+    sr[j] = sv;
+    mr[j] = mv;
+    float score = cat_st_gumbel<float>(mv, ur[j]);
+    if (score > best) {
+      best = score;
+      best_j = j;
+    }
+  }
+  for (int j = 0; j < KD; ++j) zr[j] = (__hip_bfloat16)(j == best_j ? 1.f : 0.f);
+}
+
+// Lane-per-column backward: lane c holds column c of a row whose KD-wide
+// groups (KD a power of two <= 64) sit on aligned lane runs.  t_j of a valid
+// column comes from cat_st_col_t (gon2 = 0.f when absent); invalid lanes pass
+// t = sj = 0.  Returns g_L.
+__device__ __forceinline__ float cat_st_col_t(float gm, float sj, float gon, float gon2, int KD, float unimix) {
+  return gm / cat_st_mix(sj, KD, unimix) + gon + gon2;
+}
+__device__ __forceinline__ float cat_st_col_bwd(float t, float sj, bool valid, int KD, float unimix) {
+  float acc = t * sj;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    if (off < KD) acc += __shfl_xor(acc, off, 64);
+  }
+  return valid ? (1.f - unimix) * sj * (t - acc) : 0.f;
 }
 
 // ---------------------------------------------------------------------------
@@ -1974,8 +2098,25 @@ void adam_step(std::vector<torch::Tensor> params, std::vector<torch::Tensor> gra
 // fused unimix-categorical straight-through head
 // rows of K logits: p = (1-u)*softmax(L) + u/K ; m = log p ;
 // sample = onehot(argmax(m + gumbel)) (or argmax(m) when !SAMPLE).
-// One wave per row (K <= 64 lanes, looped above that).
+// One wave per row (K <= 64 lanes, looped above that); the math is the
+// cat_st_wave_fwd / cat_st_wave_bwd cores.
 // ---------------------------------------------------------------------------
+
+// grid for one wave per row: blocks of kBlock/64 waves
+static int wave_row_blocks(long rows) {
+  const int waves_per_block = kBlock / 64;
+  return (int)((rows + waves_per_block - 1) / waves_per_block);
+}
+
+// runs launch(std::true_type{}) or launch(std::false_type{}): the SAMPLE
+// template argument of the forward kernels
+template <typename F>
+static void with_sample(bool sample, F&& launch) {
+  if (sample)
+    launch(std::true_type{});
+  else
+    launch(std::false_type{});
+}
 
 template <typename T, bool SAMPLE>
 __global__ void cat_st_fwd_kernel(const T* __restrict__ raw, const float* __restrict__ urand,
@@ -1992,46 +2133,8 @@ __global__ void cat_st_fwd_kernel(const T* __restrict__ raw, const float* __rest
   // b*ohs + s*K (ohs = S*K, spb = S reproduces the contiguous layout)
   T* oh = onehot + (row / spb) * ohs + (row % spb) * (long)K;
   T* oh2 = onehot2 ? onehot2 + (row / spb) * oh2s + (row % spb) * (long)K : nullptr;
-  // row max
-  float lmax = -1e30f;
-  for (int j = lane; j < K; j += 64) lmax = fmaxf(lmax, ld(L, j));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
-  // exp + sum
-  float lsum = 0.f;
-  for (int j = lane; j < K; j += 64) lsum += texp<T>(ld(L, j) - lmax);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
-  const float inv = 1.f / lsum;
-  // p, m, gumbel-argmax
-  float best = -1e30f;
-  int best_j = 0;
-  for (int j = lane; j < K; j += 64) {
-    float s = texp<T>(ld(L, j) - lmax) * inv;
-    float p = (1.f - unimix) * s + unimix / K;
-    float m = tlog<T>(p);
-    sr[j] = s;
-    mr[j] = m;
-    float score = m;
-    if (SAMPLE) {
-      float u = urand[row * (long)K + j];
-      float t = fmaxf(-tlog<T>(fmaxf(u, 1e-20f)), 1e-20f);
-      score += -tlog<T>(t);  // Gumbel(0,1) noise
-    }
-    if (score > best) {
-      best = score;
-      best_j = j;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    float ob = __shfl_xor(best, off, 64);
-    int oj = __shfl_xor(best_j, off, 64);
-    if (ob > best || (ob == best && oj < best_j)) {
-      best = ob;
-      best_j = oj;
-    }
-  }
+  const float* ur = SAMPLE ? urand + row * (long)K : nullptr;
+  const int best_j = cat_st_wave_fwd<T, SAMPLE>(L, ur, mr, sr, K, unimix, lane);
   for (int j = lane; j < K; j += 64) {
     const float z = j == best_j ? 1.f : 0.f;
     st(oh, j, z);
@@ -2063,40 +2166,7 @@ __global__ void cat_st_resets_fwd_kernel(
   T* oh = onehot + row * (long)K;
   const float fb = ld(f, b);
   const int SK = S * K;
-  float lmax = -1e30f;
-  for (int j = lane; j < K; j += 64) lmax = fmaxf(lmax, ld(L, j));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
-  float lsum = 0.f;
-  for (int j = lane; j < K; j += 64) lsum += texp<T>(ld(L, j) - lmax);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
-  const float inv = 1.f / lsum;
-  float best = -1e30f;
-  int best_j = 0;
-  for (int j = lane; j < K; j += 64) {
-    float sv = texp<T>(ld(L, j) - lmax) * inv;
-    float p = (1.f - unimix) * sv + unimix / K;
-    float m = tlog<T>(p);
-    sr[j] = sv;
-    mr[j] = m;
-    float u = urand[row * (long)K + j];
-    float t = fmaxf(-tlog<T>(fmaxf(u, 1e-20f)), 1e-20f);
-    float score = m - tlog<T>(t);
-    if (score > best) {
-      best = score;
-      best_j = j;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    float ob = __shfl_xor(best, off, 64);
-    int oj = __shfl_xor(best_j, off, 64);
-    if (ob > best || (ob == best && oj < best_j)) {
-      best = ob;
-      best_j = oj;
-    }
-  }
+  const int best_j = cat_st_wave_fwd<T, true>(L, urand + row * (long)K, mr, sr, K, unimix, lane);
   for (int j = lane; j < K; j += 64) {
     const float z = j == best_j ? 1.f : 0.f;
     st(oh, j, z);
@@ -2125,8 +2195,7 @@ void cat_st_resets_fwd(const torch::Tensor& raw, const torch::Tensor& urand, dou
   int H = (int)ih.size(1);
   TORCH_CHECK(H % S == 0, "cat_st_resets_fwd requires H % S == 0");
   TORCH_CHECK(S * K == (int)iz.size(1), "iz must be [B, S*K]");
-  const int rows_per_block = kBlock / 64;
-  int blocks = (int)((nrows + rows_per_block - 1) / rows_per_block);
+  const int blocks = wave_row_blocks(nrows);
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_resets_fwd", [&] {
     using T = scalar_t;
@@ -2154,21 +2223,8 @@ __global__ void cat_st_bwd_kernel(const float* __restrict__ gm, const T* __restr
   const T* gor2 = gon2 ? gon2 + row * (long)K : nullptr;
   const float* sr = s_saved + row * (long)K;
   T* gr = graw + row * (long)K;
-  float acc = 0.f;
-  for (int j = lane; j < K; j += 64) {
-    float sj = sr[j];
-    float pj = (1.f - unimix) * sj + unimix / K;
-    float t = gmr[j] / pj + ld(gor, j) + (gor2 ? ld(gor2, j) : 0.f);
-    acc += t * sj;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  for (int j = lane; j < K; j += 64) {
-    float sj = sr[j];
-    float pj = (1.f - unimix) * sj + unimix / K;
-    float t = gmr[j] / pj + ld(gor, j) + (gor2 ? ld(gor2, j) : 0.f);
-    st(gr, j, (1.f - unimix) * sj * (t - acc));
-  }
+  cat_st_wave_bwd(gmr, sr, gr, K, unimix, lane,
+                  [&](int j, float a, bool) { return a + ld(gor, j) + (gor2 ? ld(gor2, j) : 0.f); });
 }
 
 // cat_st backward for step t fused with scan_resets_bwd of step t+1: the
@@ -2195,24 +2251,13 @@ __global__ void cat_st_resets_bwd_kernel(
   const T* gor = gon + row * (long)K;
   const float* sr = s_saved + row * (long)K;
   T* gr = graw + row * (long)K;
-  float acc = 0.f;
-  for (int j = lane; j < K; j += 64) {
-    float sj = sr[j];
-    float pj = (1.f - unimix) * sj + unimix / K;
+  // the z-carry term (1-f)*gx is formed in-register; the reduction pass also
+  // banks the masked part f*gx into giz_acc (one update per element)
+  cat_st_wave_bwd(gmr, sr, gr, K, unimix, lane, [&](int j, float a, bool first) {
     float gxv = ld(gx, b * gxs + s * K + j);
-    giz_acc[b * (long)SK + s * K + j] += fb * gxv;
-    float t = gmr[j] / pj + ld(gor, j) + (1.f - fb) * gxv;
-    acc += t * sj;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  for (int j = lane; j < K; j += 64) {
-    float sj = sr[j];
-    float pj = (1.f - unimix) * sj + unimix / K;
-    float gxv = ld(gx, b * gxs + s * K + j);
-    float t = gmr[j] / pj + ld(gor, j) + (1.f - fb) * gxv;
-    st(gr, j, (1.f - unimix) * sj * (t - acc));
-  }
+    if (first) giz_acc[b * (long)SK + s * K + j] += fb * gxv;
+    return a + ld(gor, j) + (1.f - fb) * gxv;
+  });
   if (s == S - 1)
     for (int j = lane; j < A; j += 64) st(ga, b * (long)A + j, (1.f - fb) * ld(gx, b * gxs + SK + j));
   const int HS = H / S;  // caller guarantees H % S == 0
@@ -2236,8 +2281,7 @@ void cat_st_resets_bwd(const torch::Tensor& gm, const torch::Tensor& gon, const 
   int A = (int)ga.size(1);
   int H = (int)gh_carry.size(1);
   TORCH_CHECK(H % S == 0, "cat_st_resets_bwd requires H % S == 0");
-  const int rows_per_block = kBlock / 64;
-  int blocks = (int)((nrows + rows_per_block - 1) / rows_per_block);
+  const int blocks = wave_row_blocks(nrows);
   auto stream = at::cuda::getCurrentCUDAStream();
   auto gonc = gon.contiguous();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, graw.scalar_type(), "cat_st_resets_bwd", [&] {
@@ -2251,46 +2295,16 @@ void cat_st_resets_bwd(const torch::Tensor& gm, const torch::Tensor& gon, const 
   });
 }
 
-std::vector<torch::Tensor> cat_st_fwd(const torch::Tensor& raw, const c10::optional<torch::Tensor>& urand,
-                                      double unimix, bool sample) {
-  CHECK_IN(raw);
+// Forward launch shared by cat_st_fwd and cat_st_fwd_o (T = raw's dtype).  onehot is either
+// contiguous (any shape) or a 2-D [B, S*K] row-strided slice of a stacked
+// buffer (fast imagination writes z straight into the trajectory tensor);
+// onehot2 has the same [rows-of-onehot, spb*K] geometry and its own row stride.
+template <typename T>
+static void cat_st_fwd_launch(const torch::Tensor& raw, const float* up, bool sample, double unimix,
+                              torch::Tensor& m, torch::Tensor& onehot, torch::Tensor& s,
+                              const c10::optional<torch::Tensor>& onehot2) {
   int K = (int)raw.size(-1);
   long nrows = raw.numel() / K;
-  auto m = torch::empty(raw.sizes(), raw.options().dtype(at::kFloat));
-  auto s = torch::empty(raw.sizes(), raw.options().dtype(at::kFloat));
-  auto onehot = torch::empty_like(raw);
-  const int rows_per_block = kBlock / 64;
-  int blocks = (int)((nrows + rows_per_block - 1) / rows_per_block);
-  auto stream = at::cuda::getCurrentCUDAStream();
-  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_fwd", [&] {
-    using T = scalar_t;
-    const float* up = urand.has_value() ? urand->data_ptr<float>() : nullptr;
-    if (sample)
-      hipLaunchKernelGGL((cat_st_fwd_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                         (const T*)raw.data_ptr(), up, m.data_ptr<float>(), (T*)onehot.data_ptr(),
-                         s.data_ptr<float>(), nrows, K, (float)unimix, (long)K, 1, (T*)nullptr, 0L);
-    else
-      hipLaunchKernelGGL((cat_st_fwd_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                         (const T*)raw.data_ptr(), up, m.data_ptr<float>(), (T*)onehot.data_ptr(),
-                         s.data_ptr<float>(), nrows, K, (float)unimix, (long)K, 1, (T*)nullptr, 0L);
-  });
-  return {m, onehot, s};
-}
-
-// Out-variant for the fused scan forward: m/onehot/s are caller-provided
-// slices of stacked [T, ...] buffers (all contiguous); onehot is written in
-// the compute dtype directly (no separate cast kernel).
-void cat_st_fwd_o(const torch::Tensor& raw, const torch::Tensor& urand, double unimix, torch::Tensor m,
-                  torch::Tensor onehot, torch::Tensor s,
-                  const c10::optional<torch::Tensor>& onehot2 = c10::nullopt) {
-  CHECK_IN(raw);
-  TORCH_CHECK(m.is_contiguous() && s.is_contiguous(), "cat_st_fwd_o outputs");
-  TORCH_CHECK(onehot.scalar_type() == raw.scalar_type(), "onehot dtype must match raw");
-  int K = (int)raw.size(-1);
-  long nrows = raw.numel() / K;
-  // onehot is either contiguous (any shape) or a 2-D [B, S*K] row-strided
-  // slice of a stacked buffer (fast imagination writes z straight into the
-  // trajectory tensor)
   long ohs = (long)K, spb = 1;
   if (!onehot.is_contiguous()) {
     TORCH_CHECK(onehot.dim() == 2 && onehot.stride(1) == 1 && nrows % onehot.size(0) == 0,
@@ -2298,43 +2312,72 @@ void cat_st_fwd_o(const torch::Tensor& raw, const torch::Tensor& urand, double u
     spb = nrows / onehot.size(0);
     ohs = onehot.stride(0);
   }
-  const int rows_per_block = kBlock / 64;
-  int blocks = (int)((nrows + rows_per_block - 1) / rows_per_block);
+  T* oh2 = nullptr;
+  long oh2s = 0;
+  if (onehot2.has_value()) {
+    TORCH_CHECK(onehot2->dim() == 2 && onehot2->stride(1) == 1 && onehot2->scalar_type() == raw.scalar_type(),
+                "cat_st_fwd_o: onehot2 must be a row-strided 2-D slice");
+    oh2 = (T*)onehot2->data_ptr();
+    oh2s = onehot2->stride(0);
+  }
+  const int blocks = wave_row_blocks(nrows);
   auto stream = at::cuda::getCurrentCUDAStream();
-  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_fwd_o", [&] {
-    using T = scalar_t;
-    T* oh2 = nullptr;
-    long oh2s = 0;
-    if (onehot2.has_value()) {
-      // same [rows-of-onehot, spb*K] geometry, its own row stride
-      TORCH_CHECK(onehot2->dim() == 2 && onehot2->stride(1) == 1 &&
-                      onehot2->scalar_type() == raw.scalar_type(),
-                  "cat_st_fwd_o: onehot2 must be a row-strided 2-D slice");
-      oh2 = (T*)onehot2->data_ptr();
-      oh2s = onehot2->stride(0);
-    }
-    hipLaunchKernelGGL((cat_st_fwd_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                       (const T*)raw.data_ptr(), urand.data_ptr<float>(), m.data_ptr<float>(),
-                       (T*)onehot.data_ptr(), s.data_ptr<float>(), nrows, K, (float)unimix, ohs, spb,
-                       oh2, oh2s);
+  with_sample(sample, [&](auto smp) {
+    hipLaunchKernelGGL((cat_st_fwd_kernel<T, decltype(smp)::value>), dim3(blocks), dim3(kBlock), 0,
+                       stream.stream(), (const T*)raw.data_ptr(), up, m.data_ptr<float>(), (T*)onehot.data_ptr(),
+                       s.data_ptr<float>(), nrows, K, (float)unimix, ohs, spb, oh2, oh2s);
   });
+}
+
+std::vector<torch::Tensor> cat_st_fwd(const torch::Tensor& raw, const c10::optional<torch::Tensor>& urand,
+                                      double unimix, bool sample) {
+  CHECK_IN(raw);
+  auto m = torch::empty(raw.sizes(), raw.options().dtype(at::kFloat));
+  auto s = torch::empty(raw.sizes(), raw.options().dtype(at::kFloat));
+  auto onehot = torch::empty_like(raw);
+  const float* up = urand.has_value() ? urand->data_ptr<float>() : nullptr;
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_fwd", [&] {
+    cat_st_fwd_launch<scalar_t>(raw, up, sample, unimix, m, onehot, s, c10::nullopt);
+  });
+  return {m, onehot, s};
+}
+
+// Out-variant for the fused scan forward: m/onehot/s are caller-provided
+// slices of stacked [T, ...] buffers (m and s contiguous); onehot is written
+// in the compute dtype directly (no separate cast kernel).
+void cat_st_fwd_o(const torch::Tensor& raw, const torch::Tensor& urand, double unimix, torch::Tensor m,
+                  torch::Tensor onehot, torch::Tensor s,
+                  const c10::optional<torch::Tensor>& onehot2 = c10::nullopt) {
+  CHECK_IN(raw);
+  TORCH_CHECK(m.is_contiguous() && s.is_contiguous(), "cat_st_fwd_o outputs");
+  TORCH_CHECK(onehot.scalar_type() == raw.scalar_type(), "onehot dtype must match raw");
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_fwd_o", [&] {
+    cat_st_fwd_launch<scalar_t>(raw, urand.data_ptr<float>(), true, unimix, m, onehot, s, onehot2);
+  });
+}
+
+// Backward launch shared by cat_st_bwd and cat_st_bwd_o (T = graw's dtype;
+// gon contiguous, gon2 absent or contiguous).
+template <typename T>
+static void cat_st_bwd_launch(const torch::Tensor& gm, const torch::Tensor& gon,
+                              const c10::optional<torch::Tensor>& gon2, const torch::Tensor& s, double unimix,
+                              torch::Tensor& graw) {
+  int K = (int)gm.size(-1);
+  long nrows = gm.numel() / K;
+  const T* g2 = gon2.has_value() ? (const T*)gon2->data_ptr() : nullptr;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL((cat_st_bwd_kernel<T>), dim3(wave_row_blocks(nrows)), dim3(kBlock), 0, stream.stream(),
+                     gm.data_ptr<float>(), (const T*)gon.data_ptr(), g2, s.data_ptr<float>(), (T*)graw.data_ptr(),
+                     nrows, K, (float)unimix);
 }
 
 torch::Tensor cat_st_bwd(const torch::Tensor& gm, const torch::Tensor& gon, const torch::Tensor& s,
                          double unimix) {
   CHECK_IN(gm);
-  int K = (int)gm.size(-1);
-  long nrows = gm.numel() / K;
   auto graw = torch::empty(gm.sizes(), gm.options().dtype(gon.scalar_type()));
-  const int rows_per_block = kBlock / 64;
-  int blocks = (int)((nrows + rows_per_block - 1) / rows_per_block);
-  auto stream = at::cuda::getCurrentCUDAStream();
   auto gonc = gon.contiguous();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, graw.scalar_type(), "cat_st_bwd", [&] {
-    using T = scalar_t;
-    hipLaunchKernelGGL((cat_st_bwd_kernel<T>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                       gm.data_ptr<float>(), (const T*)gonc.data_ptr(), nullptr, s.data_ptr<float>(),
-                       (T*)graw.data_ptr(), nrows, K, (float)unimix);
+    cat_st_bwd_launch<scalar_t>(gm, gonc, c10::nullopt, s, unimix, graw);
   });
   return graw;
 }
@@ -2346,26 +2389,17 @@ void cat_st_bwd_o(const torch::Tensor& gm, const torch::Tensor& gon, const c10::
   CHECK_IN(gm);
   CHECK_IN(gon);
   TORCH_CHECK(graw.is_contiguous() && graw.scalar_type() == gon.scalar_type(), "cat_st_bwd_o output");
-  int K = (int)gm.size(-1);
-  long nrows = gm.numel() / K;
-  const int rows_per_block = kBlock / 64;
-  int blocks = (int)((nrows + rows_per_block - 1) / rows_per_block);
-  auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, graw.scalar_type(), "cat_st_bwd_o", [&] {
-    using T = scalar_t;
-    const T* g2 = gon2.has_value() ? (const T*)gon2->data_ptr() : nullptr;
-    hipLaunchKernelGGL((cat_st_bwd_kernel<T>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                       gm.data_ptr<float>(), (const T*)gon.data_ptr(), g2, s.data_ptr<float>(),
-                       (T*)graw.data_ptr(), nrows, K, (float)unimix);
+    cat_st_bwd_launch<scalar_t>(gm, gon, gon2, s, unimix, graw);
   });
 }
 
 // ---------------------------------------------------------------------------
 // ragged unimix-categorical straight-through head (MultiDiscrete actors)
-// rows of A = sum_h K_h logits, head h in columns [off_h, off_h + K_h): the
-// per-head math, loop order, reductions and tie-break are cat_st_fwd_kernel's
-// verbatim (one wave per (row, head)), so every output is bit-identical to
-// the per-head kernel run on that head's column slice.  The head table rides
+// rows of A = sum_h K_h logits, head h in columns [off_h, off_h + K_h): one
+// wave per (row, head) runs the same cat_st_wave_fwd / cat_st_wave_bwd cores
+// as the per-head kernels, so every output is bit-identical to the per-head
+// kernel run on that head's column slice.  The head table rides
 // in the kernel arguments (no device table, no H2D copy: capture-safe).
 // ---------------------------------------------------------------------------
 
@@ -2409,46 +2443,7 @@ __global__ void __launch_bounds__(256)
   const float* ur = SAMPLE ? urand + row * (long)A + hoff : nullptr;
   T* oh = onehot ? onehot + row * ohs + hoff : nullptr;
   T* oh2 = onehot2 ? onehot2 + row * oh2s + hoff : nullptr;
-  // head max
-  float lmax = -1e30f;
-  for (int j = lane; j < K; j += 64) lmax = fmaxf(lmax, ld(L, j));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
-  // exp + sum
-  float lsum = 0.f;
-  for (int j = lane; j < K; j += 64) lsum += texp<T>(ld(L, j) - lmax);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
-  const float inv = 1.f / lsum;
-  // p, m, gumbel-argmax
-  float best = -1e30f;
-  int best_j = 0;
-  for (int j = lane; j < K; j += 64) {
-    float s = texp<T>(ld(L, j) - lmax) * inv;
-    float p = (1.f - unimix) * s + unimix / K;
-    float m = tlog<T>(p);
-    sr[j] = s;
-    mr[j] = m;
-    float score = m;
-    if (SAMPLE) {
-      float u = ur[j];
-      float t = fmaxf(-tlog<T>(fmaxf(u, 1e-20f)), 1e-20f);
-      score += -tlog<T>(t);  // Gumbel(0,1) noise
-    }
-    if (score > best) {
-      best = score;
-      best_j = j;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    float ob = __shfl_xor(best, off, 64);
-    int oj = __shfl_xor(best_j, off, 64);
-    if (ob > best || (ob == best && oj < best_j)) {
-      best = ob;
-      best_j = oj;
-    }
-  }
+  const int best_j = cat_st_wave_fwd<T, SAMPLE>(L, ur, mr, sr, K, unimix, lane);
   if (!oh && !oh2) return;  // log-probs only (sample=false, no destination)
   for (int j = lane; j < K; j += 64) {
     const float z = j == best_j ? 1.f : 0.f;
@@ -2472,21 +2467,8 @@ __global__ void __launch_bounds__(256)
   const T* gor = gon ? gon + row * (long)A + hoff : nullptr;
   const float* sr = s_saved + row * (long)A + hoff;
   T* gr = graw + row * (long)A + hoff;
-  float acc = 0.f;
-  for (int j = lane; j < K; j += 64) {
-    float sj = sr[j];
-    float pj = (1.f - unimix) * sj + unimix / K;
-    float t = gmr[j] / pj + (gor ? ld(gor, j) : 0.f);
-    acc += t * sj;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  for (int j = lane; j < K; j += 64) {
-    float sj = sr[j];
-    float pj = (1.f - unimix) * sj + unimix / K;
-    float t = gmr[j] / pj + (gor ? ld(gor, j) : 0.f);
-    st(gr, j, (1.f - unimix) * sj * (t - acc));
-  }
+  cat_st_wave_bwd(gmr, sr, gr, K, unimix, lane,
+                  [&](int j, float a, bool) { return a + (gor ? ld(gor, j) : 0.f); });
 }
 
 static RaggedHeads ragged_heads(const std::vector<int64_t>& sizes, int64_t A, const char* who) {
@@ -2523,16 +2505,14 @@ static void cat_st_ragged_launch(const torch::Tensor& raw, const float* up, floa
                                  int A, const RaggedHeads& heads, double unimix, long ohs, T* oh2, long oh2s,
                                  bool sample) {
   const long waves = nrows * heads.n;
-  const int waves_per_block = kBlock / 64;
-  const int blocks = (int)((waves + waves_per_block - 1) / waves_per_block);
+  const int blocks = wave_row_blocks(waves);
   if (blocks == 0) return;
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (sample)
-    hipLaunchKernelGGL((cat_st_ragged_fwd_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                       (const T*)raw.data_ptr(), up, m, oh, s, nrows, A, heads, (float)unimix, ohs, oh2, oh2s);
-  else
-    hipLaunchKernelGGL((cat_st_ragged_fwd_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                       (const T*)raw.data_ptr(), up, m, oh, s, nrows, A, heads, (float)unimix, ohs, oh2, oh2s);
+  with_sample(sample, [&](auto smp) {
+    hipLaunchKernelGGL((cat_st_ragged_fwd_kernel<T, decltype(smp)::value>), dim3(blocks), dim3(kBlock), 0,
+                       stream.stream(), (const T*)raw.data_ptr(), up, m, oh, s, nrows, A, heads, (float)unimix,
+                       ohs, oh2, oh2s);
+  });
 }
 
 static const float* ragged_urand(const c10::optional<torch::Tensor>& urand, const torch::Tensor& raw, bool sample,
@@ -2618,8 +2598,7 @@ torch::Tensor cat_st_ragged_bwd(const torch::Tensor& gm, const c10::optional<tor
   const at::ScalarType dt = gon.has_value() ? gon->scalar_type() : out_dtype.value_or(at::kFloat);
   auto graw = torch::empty(gm.sizes(), gm.options().dtype(dt));
   const long waves = nrows * heads.n;
-  const int waves_per_block = kBlock / 64;
-  const int blocks = (int)((waves + waves_per_block - 1) / waves_per_block);
+  const int blocks = wave_row_blocks(waves);
   if (blocks == 0) return graw;
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, dt, "cat_st_ragged_bwd", [&] {
@@ -3715,32 +3694,9 @@ __global__ void __launch_bounds__(256) g16_cat_st_kernel(const __hip_bfloat16* _
     const int m = task / groups;
     if (m >= B) continue;
     const int g = task - m * groups;
-    const float* row = lds + m * N + g * KD;
-    float lmax = -1e30f;
-    for (int j = 0; j < KD; ++j) lmax = fmaxf(lmax, row[j]);
-    float lsum = 0.f;
-    for (int j = 0; j < KD; ++j) lsum += expf(row[j] - lmax);
-    const float inv = 1.f / lsum;
-    const float* ur = urand + ((long)m * groups + g) * KD;
-    float* mr_ = m_out + (long)m * N + g * KD;
-    float* sr = s_out + (long)m * N + g * KD;
-    __hip_bfloat16* zr = z_out + (long)m * N + g * KD;
-    float best = -1e30f;
-    int best_j = 0;
-    for (int j = 0; j < KD; ++j) {
-      float sv = expf(row[j] - lmax) * inv;
-      float pv = (1.f - unimix) * sv + unimix / KD;
-      float mv = logf(pv);
-      sr[j] = sv;
-      mr_[j] = mv;
-      float tt = fmaxf(-logf(fmaxf(ur[j], 1e-20f)), 1e-20f);
-      float score = mv - logf(tt);
-      if (score > best) {
-        best = score;
-        best_j = j;
-      }
-    }
-    for (int j = 0; j < KD; ++j) zr[j] = (__hip_bfloat16)(j == best_j ? 1.f : 0.f);
+    const long o = (long)m * N + g * KD;
+    cat_st_group_fwd(lds + m * N + g * KD, urand + ((long)m * groups + g) * KD, m_out + o, s_out + o, z_out + o,
+                     KD, unimix);
   }
 }
 
@@ -4195,31 +4151,9 @@ __global__ void __launch_bounds__(256) pk_scan_fwd_kernel(PkParams P) {
           const int col0 = gloc * P.KD;                 // within the WG tile
           const int gcol0 = wg * 64 + col0;             // absolute column
           const int sgrp = gcol0 / P.KD;                // stochastic group index
-          float lmax = -1e30f;
-          for (int j = 0; j < P.KD; ++j) lmax = fmaxf(lmax, lds[m * 64 + col0 + j]);
-          float lsum = 0.f;
-          for (int j = 0; j < P.KD; ++j) lsum += expf(lds[m * 64 + col0 + j] - lmax);
-          const float inv = 1.f / lsum;
-          float best = -1e30f;
-          int best_j = 0;
-          const float* ur = P.urand + (((long)t * P.B + m) * P.S + sgrp) * P.KD;
-          float* mr = P.m_seq + ((long)t * P.B + m) * P.SK + gcol0;
-          float* sr = P.s_s + ((long)t * P.B + m) * P.SK + gcol0;
-          __hip_bfloat16* zr = P.z_seq + ((long)t * P.B + m) * P.SK + gcol0;
-          for (int j = 0; j < P.KD; ++j) {
-            float sv = expf(lds[m * 64 + col0 + j] - lmax) * inv;
-            float pv = (1.f - P.unimix) * sv + P.unimix / P.KD;
-            float mv = logf(pv);
-            sr[j] = sv;
-            mr[j] = mv;
-            float tt = fmaxf(-logf(fmaxf(ur[j], 1e-20f)), 1e-20f);
-            float score = mv - logf(tt);
-            if (score > best) {
-              best = score;
-              best_j = j;
-            }
-          }
-          for (int j = 0; j < P.KD; ++j) zr[j] = (__hip_bfloat16)(j == best_j ? 1.f : 0.f);
+          const long o = ((long)t * P.B + m) * P.SK + gcol0;
+          cat_st_group_fwd(lds + m * 64 + col0, P.urand + (((long)t * P.B + m) * P.S + sgrp) * P.KD, P.m_seq + o,
+                           P.s_s + o, P.z_seq + o, P.KD, P.unimix);
         }
         __syncthreads();
       }
@@ -4780,31 +4714,8 @@ __global__ void __launch_bounds__(256) scan2_catst_kernel(
     const int gl = task - m * gpw;
     const float* row = raw + m * 64 + gl * KD;
     const long gcol = (long)blockIdx.x * 64 + gl * KD;  // global col of the group
-    float lmax = -1e30f;
-    for (int j = 0; j < KD; ++j) lmax = fmaxf(lmax, row[j]);
-    float lsum = 0.f;
-    for (int j = 0; j < KD; ++j) lsum += expf(row[j] - lmax);
-    const float inv = 1.f / lsum;
-    const float* ur = urand + (long)m * SK + gcol;
-    float* mro = m_out + (long)m * SK + gcol;
-    float* sro = s_out + (long)m * SK + gcol;
-    __hip_bfloat16* zro = z_out + (long)m * SK + gcol;
-    float best = -1e30f;
-    int best_j = 0;
-    for (int j = 0; j < KD; ++j) {
-      float sv = expf(row[j] - lmax) * inv;
-      float pv = (1.f - unimix) * sv + unimix / KD;
-      float mv = logf(pv);
-      sro[j] = sv;
-      mro[j] = mv;
-      float tt = fmaxf(-logf(fmaxf(ur[j], 1e-20f)), 1e-20f);
-      float score = mv - logf(tt);
-      if (score > best) {
-        best = score;
-        best_j = j;
-      }
-    }
-    for (int j = 0; j < KD; ++j) zro[j] = (__hip_bfloat16)(j == best_j ? 1.f : 0.f);
+    const long o = (long)m * SK + gcol;
+    cat_st_group_fwd(row, urand + o, m_out + o, s_out + o, z_out + o, KD, unimix);
   }
 }
 
@@ -4836,15 +4747,10 @@ __global__ void __launch_bounds__(256) scan2_b4_kernel(
       if (m < B) {
         const long idx = (long)m * SK + c;
         sj = s_saved[idx];
-        float pj = (1.f - unimix) * sj + unimix / KD;
-        t = gm[idx] / pj + __bfloat162float(gon[idx]) + (gon2 ? __bfloat162float(gon2[idx]) : 0.f);
+        t = cat_st_col_t(gm[idx], sj, __bfloat162float(gon[idx]), gon2 ? __bfloat162float(gon2[idx]) : 0.f, KD,
+                         unimix);
       }
-      float acc = t * sj;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        if (off < KD) acc += __shfl_xor(acc, off, 64);
-      }
-      graw[m * KP + c] = __float2bfloat16(m < B ? (1.f - unimix) * sj * (t - acc) : 0.f);
+      graw[m * KP + c] = __float2bfloat16(cat_st_col_bwd(t, sj, m < B, KD, unimix));
     }
   }
   __syncthreads();
@@ -5540,31 +5446,8 @@ __global__ void __launch_bounds__(256) scan3_catst_kernel(
     const int gl = task - m * gpw;
     const float* row = &raw[m][gl * KD];
     const long gcol = (long)tile * 64 + gl * KD;
-    float lmax = -1e30f;
-    for (int j = 0; j < KD; ++j) lmax = fmaxf(lmax, row[j]);
-    float lsum = 0.f;
-    for (int j = 0; j < KD; ++j) lsum += expf(row[j] - lmax);
-    const float inv = 1.f / lsum;
-    const float* ur = urand + (long)m * SK + gcol;
-    float* mro = m_out + (long)m * SK + gcol;
-    float* sro = s_out + (long)m * SK + gcol;
-    __hip_bfloat16* zro = z_out + (long)m * SK + gcol;
-    float best = -1e30f;
-    int best_j = 0;
-    for (int j = 0; j < KD; ++j) {
-      float sv = expf(row[j] - lmax) * inv;
-      float pv = (1.f - unimix) * sv + unimix / KD;
-      float mv = logf(pv);
-      sro[j] = sv;
-      mro[j] = mv;
-      float tt = fmaxf(-logf(fmaxf(ur[j], 1e-20f)), 1e-20f);
-      float score = mv - logf(tt);
-      if (score > best) {
-        best = score;
-        best_j = j;
-      }
-    }
-    for (int j = 0; j < KD; ++j) zro[j] = (__hip_bfloat16)(j == best_j ? 1.f : 0.f);
+    const long o = (long)m * SK + gcol;
+    cat_st_group_fwd(row, urand + o, m_out + o, s_out + o, z_out + o, KD, unimix);
   }
 }
 
@@ -5602,15 +5485,11 @@ __global__ void __launch_bounds__(256) scan3_b4_kernel(
       if (m < B && c < KL) {
         const long idx = (long)m * SK + kbeg0 + c;
         sj = s_saved[idx];
-        float pj = (1.f - unimix) * sj + unimix / KD;
-        t = gm[idx] / pj + __bfloat162float(gon[idx]) + (gon2 ? __bfloat162float(gon2[idx]) : 0.f);
+        t = cat_st_col_t(gm[idx], sj, __bfloat162float(gon[idx]), gon2 ? __bfloat162float(gon2[idx]) : 0.f, KD,
+                         unimix);
       }
-      float acc = t * sj;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        if (off < KD) acc += __shfl_xor(acc, off, 64);
-      }
-      if (c < KLP) graw[m * KLP + c] = __float2bfloat16((m < B && c < KL) ? (1.f - unimix) * sj * (t - acc) : 0.f);
+      const float g = cat_st_col_bwd(t, sj, m < B && c < KL, KD, unimix);
+      if (c < KLP) graw[m * KLP + c] = __float2bfloat16(g);
     }
     // zero the 32-align padding tail
     for (int c = KL + lane; c < KLP; c += 64) graw[m * KLP + c] = (__hip_bfloat16)0.f;
