@@ -23,6 +23,7 @@ bit-identical per head to the single-head kernel
 
 from __future__ import annotations
 
+import os
 from typing import Any, Tuple
 
 import torch
@@ -123,8 +124,14 @@ def imagine_rollout(
     tp = torch.empty(B, P, device=dev, dtype=dt)
     traw = torch.empty(B, SK, device=dev, dtype=dt)
     mr = torch.empty(2, B, device=dev, dtype=torch.float32)
-    m_tmp = torch.empty(B, SK, device=dev, dtype=torch.float32)
-    s_tmp = torch.empty(B, S, K, device=dev, dtype=torch.float32)
+    # the transition and single-head action samples are inference only: the
+    # sampler without the fp32 log-prob / softmax outputs
+    # (SHEEPRL_AMD_CAT_SAMPLE=0: cat_st_fwd_o and its two scratch outputs;
+    # same one-hots either way)
+    sample_only = os.environ.get("SHEEPRL_AMD_CAT_SAMPLE", "1") != "0"
+    if not sample_only:
+        m_tmp = torch.empty(B, S, K, device=dev, dtype=torch.float32)
+        s_tmp = torch.empty(B, S, K, device=dev, dtype=torch.float32)
     am_tmp = torch.empty(B, A, device=dev, dtype=torch.float32)
     as_tmp = torch.empty(B, A, device=dev, dtype=torch.float32)
     a_hidden = [torch.empty(B, b.linear.out_features, device=dev, dtype=dt) for b in actor_blocks]
@@ -139,7 +146,9 @@ def imagine_rollout(
             x = hid
         torch.addmm(head_b, x, head_w.t(), out=alogits)
         # the sampled action ALSO lands in the next step's GEMM input slice
-        if len(heads) == 1:
+        if len(heads) == 1 and sample_only:
+            ext.cat_st_sample_o(alogits, urand_a[i], a_unimix, acts[i], xs[:, SK:])
+        elif len(heads) == 1:
             ext.cat_st_fwd_o(alogits, urand_a[i], a_unimix, am_tmp, acts[i], as_tmp, xs[:, SK:])
         else:
             ext.cat_st_ragged_fwd_o(alogits, urand_a[i], head_sizes, a_unimix, True, am_tmp, as_tmp, acts[i],
@@ -166,8 +175,11 @@ def imagine_rollout(
         torch.mm(h_buf, wt1.t(), out=tg)
         ext.ln_act_fwd_o(tg, trans[0].ln_weight, trans[0].ln_bias, trans[0].ln_eps, True, tp, mr[0], mr[1])
         torch.addmm(bt2, tp, wt2.t(), out=traw)
-        ext.cat_st_fwd_o(traw.view(B, S, K), urand_t[i - 1], unimix, m_tmp.view(B, S, K),
-                         traj[i][:, :SK], s_tmp, xs[:, :SK])
+        if sample_only:
+            ext.cat_st_sample_o(traw.view(B, S, K), urand_t[i - 1], unimix, traj[i][:, :SK], xs[:, :SK])
+        else:
+            ext.cat_st_fwd_o(traw.view(B, S, K), urand_t[i - 1], unimix, m_tmp, traj[i][:, :SK], s_tmp,
+                             xs[:, :SK])
         # --- policy on the new latent ---
         actor_step(i)
     return traj, acts

@@ -144,27 +144,33 @@ __device__ __forceinline__ float cat_st_gumbel(float m, float u) {
   return m - tlog<T>(t);
 }
 
-// Wave forward: the 64 lanes of a wave stride over one row of K logits.
-// Writes sr[j] = s and mr[j] = m, returns the wave-uniform sampled index
-// (argmax of m when !SAMPLE; ur is not read then).
-template <typename T, bool SAMPLE>
+// Wave forward: an aligned group of G lanes (a whole wave by default) strides
+// over one row of K logits; `lane` is the lane's index within its group.
+// Writes sr[j] = s and mr[j] = m when STORE, returns the group-uniform sampled
+// index (argmax of m when !SAMPLE; ur is not read then).  Idle lanes hold the
+// reductions' neutral values (0, -1e30), so for K <= G < 64 the G-lane
+// butterflies give the bits of the 64-lane ones.
+template <typename T, bool SAMPLE, int G = 64, bool STORE = true>
 __device__ __forceinline__ int cat_st_wave_fwd(const T* L, const float* ur, float* mr, float* sr, int K,
                                                float unimix, int lane) {
   float lmax = -1e30f;
-  for (int j = lane; j < K; j += 64) lmax = fmaxf(lmax, ld(L, j));
+  for (int j = lane; j < K; j += G) lmax = fmaxf(lmax, ld(L, j));
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
+  for (int off = G / 2; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
   float lsum = 0.f;
-  for (int j = lane; j < K; j += 64) lsum += texp<T>(ld(L, j) - lmax);
-  lsum = wave_sum(lsum);
+  for (int j = lane; j < K; j += G) lsum += texp<T>(ld(L, j) - lmax);
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
   const float inv = 1.f / lsum;
   float best = -1e30f;
   int best_j = 0;
-  for (int j = lane; j < K; j += 64) {
+  for (int j = lane; j < K; j += G) {
     float s = texp<T>(ld(L, j) - lmax) * inv;
     float m = tlog<T>(cat_st_mix(s, K, unimix));
-    sr[j] = s;
-    mr[j] = m;
+    if (STORE) {
+      sr[j] = s;
+      mr[j] = m;
+    }
     float score = m;
     if (SAMPLE) score = cat_st_gumbel<T>(m, ur[j]);
     if (score > best) {
@@ -173,7 +179,7 @@ __device__ __forceinline__ int cat_st_wave_fwd(const T* L, const float* ur, floa
     }
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
+  for (int off = G / 2; off > 0; off >>= 1) {
     float ob = __shfl_xor(best, off, 64);
     int oj = __shfl_xor(best_j, off, 64);
     if (ob > best || (ob == best && oj < best_j)) {
@@ -843,6 +849,28 @@ int ln_cl_lanes(int D, long stride) {
   return 0;
 }
 
+// Few-row routing of the LayerNorm BACKWARD: the channels-last kernel packs
+// 64/L rows per wave for million-row conv LayerNorms; at the scan's row counts
+// that leaves a handful of blocks on a latency floor, and the block-per-row
+// kernels are faster.  Row counts at or below the limit skip the
+// channels-last path.  Measured in-graph, D=512 bf16 contiguous,
+// channels-last vs row kernels (us):
+//   backward  N=16 8.60/3.71  N=64 8.82/4.88  N=256 9.97/10.46  N=1024 13.1/15.4
+//   forward   N=16 3.18/2.79  N=64 3.24/2.93  N=256 3.26/2.96   N=1024 3.40/3.05
+// so the backward crosses over between 64 and 256 rows.  The forward keeps
+// its stride-only routing: 0.3 us is not worth a different rounding of
+// activations that feed categorical samples (few-row forwards: the player,
+// the scan's third LN at small model sizes).
+// SHEEPRL_AMD_LN_FEW_ROWS (read once) overrides the limit; 0 restores the
+// stride-only routing.
+long ln_few_rows() {
+  static const long kLimit = [] {
+    const char* s = getenv("SHEEPRL_AMD_LN_FEW_ROWS");
+    return s ? atol(s) : 64L;
+  }();
+  return kLimit;
+}
+
 template <typename T, typename TW, bool SILU>
 void launch_ln_fwd_cl(int L, long R, hipStream_t st, const T* x, const TW* w, const TW* b, T* y, float* mo,
                       float* ro, int D, float eps) {
@@ -1198,7 +1226,7 @@ void ln_act_bwd_core(const torch::Tensor& gy, const torch::Tensor& x, const torc
       using T = scalar_t;
       AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, wc.scalar_type(), "ln_act_bwd_cl_w", [&] {
         using TW = scalar_t;
-        const int L = ln_cl_lanes<T>(D, gys);
+        const int L = N <= ln_few_rows() ? 0 : ln_cl_lanes<T>(D, gys);
         if (L) {
           if (silu)
             launch_ln_bwd_cl<T, TW, true>(L, N, streamv.stream(), (const T*)gy.data_ptr(),
@@ -2355,6 +2383,86 @@ void cat_st_fwd_o(const torch::Tensor& raw, const torch::Tensor& urand, double u
     cat_st_fwd_launch<scalar_t>(raw, urand.data_ptr<float>(), true, unimix, m, onehot, s, onehot2);
   });
 }
+
+// Inference-only sampler (the no-grad imagination rollout): the one-hots of
+// cat_st_fwd_o without its fp32 m/s outputs.  A row takes an aligned group of
+// G lanes (G = next power of two >= K, at most 64), so 64/G rows share a
+// wave; the math is cat_st_wave_fwd's, hence the same one-hots bit for bit.
+template <typename T, int G>
+__global__ void __launch_bounds__(256)
+    cat_st_sample_kernel(const T* __restrict__ raw, const float* __restrict__ urand, T* __restrict__ onehot,
+                         long nrows, int K, float unimix, long ohs, long spb, T* __restrict__ onehot2,
+                         long oh2s) {
+  const int lane = threadIdx.x & (G - 1);
+  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  // groups past the last row recompute it and store nothing: every lane of
+  // the wave stays in the shuffles
+  const bool live = row < nrows;
+  if (!live) row = nrows - 1;
+  const T* L = raw + row * (long)K;
+  const int best_j =
+      cat_st_wave_fwd<T, true, G, false>(L, urand + row * (long)K, nullptr, nullptr, K, unimix, lane);
+  if (!live) return;
+  // same [B, S*K] row-strided geometry as cat_st_fwd_kernel
+  T* oh = onehot + (row / spb) * ohs + (row % spb) * (long)K;
+  T* oh2 = onehot2 ? onehot2 + (row / spb) * oh2s + (row % spb) * (long)K : nullptr;
+  for (int j = lane; j < K; j += G) {
+    const float z = j == best_j ? 1.f : 0.f;
+    st(oh, j, z);
+    if (oh2) st(oh2, j, z);
+  }
+}
+
+#define SHEEP_CAT_SAMPLE_CASE(GV)                                                                          \
+  case GV:                                                                                                 \
+    hipLaunchKernelGGL((cat_st_sample_kernel<T, GV>), dim3(blocks), dim3(kBlock), 0, stream.stream(),      \
+                       (const T*)raw.data_ptr(), urand.data_ptr<float>(), (T*)onehot.data_ptr(), nrows, K, \
+                       (float)unimix, ohs, spb, (T*)oh2, oh2s);                                            \
+    break;
+void cat_st_sample_o(const torch::Tensor& raw, const torch::Tensor& urand, double unimix, torch::Tensor onehot,
+                     const c10::optional<torch::Tensor>& onehot2 = c10::nullopt) {
+  CHECK_IN(raw);
+  CHECK_IN(urand);
+  TORCH_CHECK(urand.scalar_type() == at::kFloat && urand.numel() == raw.numel(), "cat_st_sample_o: urand");
+  TORCH_CHECK(onehot.scalar_type() == raw.scalar_type(), "onehot dtype must match raw");
+  const int K = (int)raw.size(-1);
+  const long nrows = raw.numel() / K;
+  if (nrows == 0) return;
+  long ohs = (long)K, spb = 1;
+  if (!onehot.is_contiguous()) {
+    TORCH_CHECK(onehot.dim() == 2 && onehot.stride(1) == 1 && nrows % onehot.size(0) == 0 &&
+                    onehot.size(1) * onehot.size(0) == raw.numel(),
+                "cat_st_sample_o: onehot must be contiguous or a row-strided 2-D slice");
+    spb = nrows / onehot.size(0);
+    ohs = onehot.stride(0);
+  } else {
+    TORCH_CHECK(onehot.numel() == raw.numel(), "cat_st_sample_o: onehot size");
+  }
+  void* oh2 = nullptr;
+  long oh2s = 0;
+  if (onehot2.has_value()) {
+    TORCH_CHECK(onehot2->dim() == 2 && onehot2->stride(1) == 1 && onehot2->scalar_type() == raw.scalar_type() &&
+                    onehot2->size(0) * spb == nrows && onehot2->size(1) == spb * K,
+                "cat_st_sample_o: onehot2 must be a row-strided 2-D slice of onehot's geometry");
+    oh2 = onehot2->data_ptr();
+    oh2s = onehot2->stride(0);
+  }
+  int G = 4;
+  while (G < K && G < 64) G <<= 1;
+  const int blocks = (int)((nrows * G + kBlock - 1) / kBlock);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_sample_o", [&] {
+    using T = scalar_t;
+    switch (G) {
+      SHEEP_CAT_SAMPLE_CASE(4)
+      SHEEP_CAT_SAMPLE_CASE(8)
+      SHEEP_CAT_SAMPLE_CASE(16)
+      SHEEP_CAT_SAMPLE_CASE(32)
+      SHEEP_CAT_SAMPLE_CASE(64)
+    }
+  });
+}
+#undef SHEEP_CAT_SAMPLE_CASE
 
 // Backward launch shared by cat_st_bwd and cat_st_bwd_o (T = graw's dtype;
 // gon contiguous, gon2 absent or contiguous).
@@ -6760,6 +6868,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_gates_bwd_acc", &gru_gates_bwd_acc);
   m.def("cat_st_fwd_o", &cat_st_fwd_o, py::arg("raw"), py::arg("urand"), py::arg("unimix"),
         py::arg("m"), py::arg("onehot"), py::arg("s"), py::arg("onehot2") = c10::nullopt);
+  m.def("cat_st_sample_o", &cat_st_sample_o, py::arg("raw"), py::arg("urand"), py::arg("unimix"),
+        py::arg("onehot"), py::arg("onehot2") = c10::nullopt);
   m.def("cat_st_bwd_o", &cat_st_bwd_o);
   m.attr("MAX_RAGGED_HEADS") = kMaxRaggedHeads;
   m.def("cat_st_ragged_fwd", &cat_st_ragged_fwd, py::arg("raw"), py::arg("urand"), py::arg("sizes"),
