@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <string>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
@@ -27,6 +29,24 @@
 namespace {
 
 constexpr int kBlock = 256;
+
+// Host-side choice of a kernel's compile-time template argument from a
+// runtime value, so each launch is written once:
+//   with_bool(flag, f)     calls f(std::true_type{}) or f(std::false_type{});
+//   with_int<2, 4>(k, f)   calls f(std::integral_constant<int, k>{}) for the
+//                          listed value equal to k; returns false if none is.
+// Inside f, decltype(arg)::value is the constant.
+template <typename F>
+void with_bool(bool flag, F&& f) {
+  if (flag)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+template <int... Vs, typename F>
+bool with_int(long v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 
 // fast transcendental variants for the bf16/half kernel instantiations:
 // v_exp_f32 (~2 instructions) vs libm expf (~16); relative error ~1e-6 is
@@ -836,9 +856,8 @@ __global__ void __launch_bounds__(kBlock) ln_act_bwd_v_kernel(const T* __restric
 }
 
 // returns L (lanes per row) when the vectorized channels-last path applies
-template <typename T>
-int ln_cl_lanes(int D, long stride) {
-  constexpr int V = 16 / sizeof(T);
+int ln_cl_lanes(int D, long stride, int itemsize) {
+  const int V = 16 / itemsize;
   if (stride != D || D % V != 0) return 0;
   int L = D / V;
   if (L < 2 || L > 64) return 0;
@@ -846,6 +865,17 @@ int ln_cl_lanes(int D, long stride) {
   // non-pow2 lane groups supported for the conv channel widths (96/192
   // bf16 -> L=12/24): floor(64/L) rows per wave, tail lanes idle
   if (L == 12 || L == 24) return L;
+  return 0;
+}
+
+// returns K (16-byte loads per lane) when the vectorized wave-per-row path
+// applies: more than 64 rows, 16-byte-aligned rows, D = K*V*nlanes with
+// nlanes <= 64; K=2 is preferred over K=4
+int ln_vec_loads(long N, int D, long stride, int itemsize) {
+  const int V = 16 / itemsize;
+  if (N <= 64 || stride % V != 0) return 0;
+  for (int K : {2, 4})
+    if (D % (K * V) == 0 && D / (K * V) <= 64) return K;
   return 0;
 }
 
@@ -871,27 +901,50 @@ long ln_few_rows() {
   return kLimit;
 }
 
+// Which LayerNorm(+SiLU) kernel a [N, D] operand with the given row stride
+// takes.  First match wins:
+//   forward : CL (stride == D), VEC (N > 64), SMALL (D <= 256), ROW
+//   backward: CL (stride == D and N > few_rows), SMALL (D <= 256), VEC, ROW
+// So the directions disagree for a row-strided (or non-CL) D <= 256 operand
+// with N > 64 and 16-byte-aligned rows: VEC forward, SMALL backward.  Kept as
+// found; aligning them changes which kernel rounds an activation.
+// param is L for CL, K for VEC; cached is the row kernels' N <= 64 argument.
+struct LnRoute {
+  enum Kind { CL, VEC, SMALL, ROW } kind;
+  int param;
+  bool cached;
+};
+LnRoute ln_route(long N, int D, long stride, int itemsize, bool backward, long few_rows) {
+  const bool cached = N <= 64;
+  if (const int L = (backward && N <= few_rows) ? 0 : ln_cl_lanes(D, stride, itemsize))
+    return {LnRoute::CL, L, cached};
+  const int K = ln_vec_loads(N, D, stride, itemsize);
+  const bool small = D <= 256;
+  if (backward && small) return {LnRoute::SMALL, 0, cached};
+  if (K) return {LnRoute::VEC, K, cached};
+  if (small) return {LnRoute::SMALL, 0, cached};
+  return {LnRoute::ROW, 0, cached};
+}
+
+// Python-visible query (no device call): (kind, param, cached); few_rows < 0
+// means the process's ln_few_rows()
+std::tuple<std::string, int, bool> ln_act_route(long N, long D, long stride, long itemsize, bool backward,
+                                                long few_rows) {
+  TORCH_CHECK(itemsize == 2 || itemsize == 4 || itemsize == 8, "ln_act_route: itemsize must be 2, 4 or 8");
+  const LnRoute r = ln_route(N, (int)D, stride, (int)itemsize, backward, few_rows < 0 ? ln_few_rows() : few_rows);
+  static const char* const kNames[] = {"CL", "VEC", "SMALL", "ROW"};
+  return {kNames[r.kind], r.param, r.cached};
+}
+
 template <typename T, typename TW, bool SILU>
 void launch_ln_fwd_cl(int L, long R, hipStream_t st, const T* x, const TW* w, const TW* b, T* y, float* mo,
                       float* ro, int D, float eps) {
   int rpb = (kBlock / 64) * (64 / L);
   int blocks = (int)std::min((R + rpb - 1) / rpb, (long)2048);
-#define SHEEP_LN_FWD_CASE(LV)                                                                              \
-  case LV:                                                                                                 \
-    hipLaunchKernelGGL((ln_act_fwd_cl_kernel<T, TW, SILU, LV>), dim3(blocks), dim3(kBlock), 0, st, x, w, b, \
-                       y, mo, ro, R, D, eps);                                                              \
-    break;
-  switch (L) {
-    SHEEP_LN_FWD_CASE(2)
-    SHEEP_LN_FWD_CASE(4)
-    SHEEP_LN_FWD_CASE(8)
-    SHEEP_LN_FWD_CASE(12)
-    SHEEP_LN_FWD_CASE(16)
-    SHEEP_LN_FWD_CASE(24)
-    SHEEP_LN_FWD_CASE(32)
-    SHEEP_LN_FWD_CASE(64)
-  }
-#undef SHEEP_LN_FWD_CASE
+  with_int<2, 4, 8, 12, 16, 24, 32, 64>(L, [&](auto lanes) {
+    hipLaunchKernelGGL((ln_act_fwd_cl_kernel<T, TW, SILU, decltype(lanes)::value>), dim3(blocks), dim3(kBlock), 0,
+                       st, x, w, b, y, mo, ro, R, D, eps);
+  });
 }
 
 template <typename T, typename TW, bool SILU>
@@ -908,22 +961,10 @@ void launch_ln_bwd_cl(int L, long R, hipStream_t st, const T* gy, const T* x, co
   }();
   blocks = (int)std::min((long)blocks, std::max(kFloor, (R + 31) / 32));
   size_t shmem = 2 * (size_t)D * sizeof(float);
-#define SHEEP_LN_BWD_CASE(LV)                                                                               \
-  case LV:                                                                                                  \
-    hipLaunchKernelGGL((ln_act_bwd_cl_kernel<T, TW, SILU, LV>), dim3(blocks), dim3(kBlock), shmem, st, gy,  \
-                       x, w, b, mean, rstd, gx, gw, gb, R, D);                                              \
-    break;
-  switch (L) {
-    SHEEP_LN_BWD_CASE(2)
-    SHEEP_LN_BWD_CASE(4)
-    SHEEP_LN_BWD_CASE(8)
-    SHEEP_LN_BWD_CASE(12)
-    SHEEP_LN_BWD_CASE(16)
-    SHEEP_LN_BWD_CASE(24)
-    SHEEP_LN_BWD_CASE(32)
-    SHEEP_LN_BWD_CASE(64)
-  }
-#undef SHEEP_LN_BWD_CASE
+  with_int<2, 4, 8, 12, 16, 24, 32, 64>(L, [&](auto lanes) {
+    hipLaunchKernelGGL((ln_act_bwd_cl_kernel<T, TW, SILU, decltype(lanes)::value>), dim3(blocks), dim3(kBlock),
+                       shmem, st, gy, x, w, b, mean, rstd, gx, gw, gb, R, D);
+  });
 }
 
 void ln_act_fwd_core(const torch::Tensor& x, const torch::Tensor& w, const torch::Tensor& b, double eps,
@@ -933,77 +974,45 @@ void ln_act_fwd_core(const torch::Tensor& x, const torch::Tensor& w, const torch
   auto wc = w.contiguous();
   auto bc = b.contiguous();
   auto stream = at::cuda::getCurrentCUDAStream();
-  const bool small = D <= 256;
+  const LnRoute r = ln_route(N, D, ys, (int)x.element_size(), false, ln_few_rows());
+  // VEC and SMALL: one wave per row, four rows per block
+  const int wblocks = (int)std::min((N + 3) / 4, (long)2048);
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, x.scalar_type(), "ln_act_fwd", [&] {
     using T = scalar_t;
     AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, wc.scalar_type(), "ln_act_fwd_w", [&] {
       using TW = scalar_t;
-      const int L = ln_cl_lanes<T>(D, ys);
-      if (L) {
-        if (silu)
-          launch_ln_fwd_cl<T, TW, true>(L, N, stream.stream(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                                        (const TW*)bc.data_ptr(), (T*)y.data_ptr(), mean.data_ptr<float>(),
-                                        rstd.data_ptr<float>(), D, (float)eps);
-        else
-          launch_ln_fwd_cl<T, TW, false>(L, N, stream.stream(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                                         (const TW*)bc.data_ptr(), (T*)y.data_ptr(), mean.data_ptr<float>(),
-                                         rstd.data_ptr<float>(), D, (float)eps);
-      } else if (int K = (N > 64 && ys % (16 / (int)sizeof(T)) == 0)
-                              ? ((D % (2 * (16 / (int)sizeof(T))) == 0 && D / (2 * (16 / (int)sizeof(T))) <= 64)
-                                     ? 2
-                                     : ((D % (4 * (16 / (int)sizeof(T))) == 0 &&
-                                         D / (4 * (16 / (int)sizeof(T))) <= 64)
-                                            ? 4
-                                            : 0))
-                              : 0) {
-        // vectorized wave-per-row (behaviour-MLP shapes): no barriers in
-        // the row loop, wave-shuffle LN stats, 16-B lane loads
-        int blocks = (int)std::min((N + 3) / 4, (long)2048);
-        if (silu) {
-          if (K == 2)
-            hipLaunchKernelGGL((ln_act_fwd_v_kernel<T, TW, true, 2>), dim3(blocks), dim3(kBlock), 0,
+      with_bool(silu, [&](auto act) {
+        constexpr bool SILU = decltype(act)::value;
+        switch (r.kind) {
+          case LnRoute::CL:
+            launch_ln_fwd_cl<T, TW, SILU>(r.param, N, stream.stream(), (const T*)x.data_ptr(),
+                                          (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), (T*)y.data_ptr(),
+                                          mean.data_ptr<float>(), rstd.data_ptr<float>(), D, (float)eps);
+            break;
+          case LnRoute::VEC:
+            // vectorized wave-per-row (behaviour-MLP shapes): no barriers in
+            // the row loop, wave-shuffle LN stats, 16-B lane loads
+            with_int<2, 4>(r.param, [&](auto loads) {
+              hipLaunchKernelGGL((ln_act_fwd_v_kernel<T, TW, SILU, decltype(loads)::value>), dim3(wblocks),
+                                 dim3(kBlock), 0, stream.stream(), (const T*)x.data_ptr(),
+                                 (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), (T*)y.data_ptr(),
+                                 mean.data_ptr<float>(), rstd.data_ptr<float>(), N, D, (float)eps, ys);
+            });
+            break;
+          case LnRoute::SMALL:
+            hipLaunchKernelGGL((ln_act_fwd_small_kernel<T, TW, SILU>), dim3(wblocks), dim3(kBlock), 0,
                                stream.stream(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
                                (const TW*)bc.data_ptr(), (T*)y.data_ptr(), mean.data_ptr<float>(),
                                rstd.data_ptr<float>(), N, D, (float)eps, ys);
-          else
-            hipLaunchKernelGGL((ln_act_fwd_v_kernel<T, TW, true, 4>), dim3(blocks), dim3(kBlock), 0,
-                               stream.stream(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                               (const TW*)bc.data_ptr(), (T*)y.data_ptr(), mean.data_ptr<float>(),
-                               rstd.data_ptr<float>(), N, D, (float)eps, ys);
-        } else {
-          if (K == 2)
-            hipLaunchKernelGGL((ln_act_fwd_v_kernel<T, TW, false, 2>), dim3(blocks), dim3(kBlock), 0,
-                               stream.stream(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                               (const TW*)bc.data_ptr(), (T*)y.data_ptr(), mean.data_ptr<float>(),
-                               rstd.data_ptr<float>(), N, D, (float)eps, ys);
-          else
-            hipLaunchKernelGGL((ln_act_fwd_v_kernel<T, TW, false, 4>), dim3(blocks), dim3(kBlock), 0,
-                               stream.stream(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                               (const TW*)bc.data_ptr(), (T*)y.data_ptr(), mean.data_ptr<float>(),
-                               rstd.data_ptr<float>(), N, D, (float)eps, ys);
+            break;
+          case LnRoute::ROW:
+            hipLaunchKernelGGL((ln_act_fwd_kernel<T, TW, SILU>), dim3((int)N), dim3(kBlock), 0, stream.stream(),
+                               (const T*)x.data_ptr(), (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
+                               (T*)y.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), D, (float)eps,
+                               ys, r.cached);
+            break;
         }
-      } else if (small) {
-        int blocks = (int)std::min((N + 3) / 4, (long)2048);
-        if (silu)
-          hipLaunchKernelGGL((ln_act_fwd_small_kernel<T, TW, true>), dim3(blocks), dim3(kBlock), 0,
-                             stream.stream(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                             (const TW*)bc.data_ptr(), (T*)y.data_ptr(), mean.data_ptr<float>(),
-                             rstd.data_ptr<float>(), N, D, (float)eps, ys);
-        else
-          hipLaunchKernelGGL((ln_act_fwd_small_kernel<T, TW, false>), dim3(blocks), dim3(kBlock), 0,
-                             stream.stream(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                             (const TW*)bc.data_ptr(), (T*)y.data_ptr(), mean.data_ptr<float>(),
-                             rstd.data_ptr<float>(), N, D, (float)eps, ys);
-      } else if (silu)
-        hipLaunchKernelGGL((ln_act_fwd_kernel<T, TW, true>), dim3((int)N), dim3(kBlock), 0, stream.stream(),
-                           (const T*)x.data_ptr(), (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
-                           (T*)y.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), D, (float)eps, ys,
-                           N <= 64);
-      else
-        hipLaunchKernelGGL((ln_act_fwd_kernel<T, TW, false>), dim3((int)N), dim3(kBlock), 0, stream.stream(),
-                           (const T*)x.data_ptr(), (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
-                           (T*)y.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), D, (float)eps, ys,
-                           N <= 64);
+      });
     });
   });
 }
@@ -1219,126 +1228,60 @@ void ln_act_bwd_core(const torch::Tensor& gy, const torch::Tensor& x, const torc
   int D = (int)x.size(1);
   auto wc = w.contiguous();
   auto bc = b.contiguous();
-  {
-    auto streamv = at::cuda::getCurrentCUDAStream();
-    bool done = false;
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, x.scalar_type(), "ln_act_bwd_cl", [&] {
-      using T = scalar_t;
-      AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, wc.scalar_type(), "ln_act_bwd_cl_w", [&] {
-        using TW = scalar_t;
-        const int L = N <= ln_few_rows() ? 0 : ln_cl_lanes<T>(D, gys);
-        if (L) {
-          if (silu)
-            launch_ln_bwd_cl<T, TW, true>(L, N, streamv.stream(), (const T*)gy.data_ptr(),
-                                          (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                                          (const TW*)bc.data_ptr(), mean.data_ptr<float>(),
-                                          rstd.data_ptr<float>(), (T*)gx.data_ptr(), gw.data_ptr<float>(),
-                                          gb.data_ptr<float>(), D);
-          else
-            launch_ln_bwd_cl<T, TW, false>(L, N, streamv.stream(), (const T*)gy.data_ptr(),
-                                           (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                                           (const TW*)bc.data_ptr(), mean.data_ptr<float>(),
-                                           rstd.data_ptr<float>(), (T*)gx.data_ptr(), gw.data_ptr<float>(),
-                                           gb.data_ptr<float>(), D);
-          done = true;
-        }
-      });
-    });
-    if (done) return;
-  }
-  if (D <= 256) {
-    size_t shmem = (size_t)(kBlock >> 6) * 2 * D * sizeof(float);
-    int blocks = (int)std::min((N + 3) / 4, (long)2048);
-    auto stream2 = at::cuda::getCurrentCUDAStream();
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, x.scalar_type(), "ln_act_bwd_s", [&] {
-      using T = scalar_t;
-      AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, wc.scalar_type(), "ln_act_bwd_s_w", [&] {
-        using TW = scalar_t;
-        if (silu)
-          hipLaunchKernelGGL((ln_act_bwd_small_kernel<T, TW, true>), dim3(blocks), dim3(kBlock), shmem,
-                             stream2.stream(), (const T*)gy.data_ptr(), (const T*)x.data_ptr(),
-                             (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), mean.data_ptr<float>(),
-                             rstd.data_ptr<float>(), (T*)gx.data_ptr(), gw.data_ptr<float>(),
-                             gb.data_ptr<float>(), N, D, gys);
-        else
-          hipLaunchKernelGGL((ln_act_bwd_small_kernel<T, TW, false>), dim3(blocks), dim3(kBlock), shmem,
-                             stream2.stream(), (const T*)gy.data_ptr(), (const T*)x.data_ptr(),
-                             (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), mean.data_ptr<float>(),
-                             rstd.data_ptr<float>(), (T*)gx.data_ptr(), gw.data_ptr<float>(),
-                             gb.data_ptr<float>(), N, D, gys);
-      });
-    });
-    return;
-  }
-  size_t shmem = (32 + 2 * (size_t)D) * sizeof(float);
-  TORCH_CHECK(shmem <= 160 * 1024, "ln_act_bwd: D too large for LDS accumulation");
-  int blocks = (int)std::min(N, (long)512);
   auto stream = at::cuda::getCurrentCUDAStream();
-  {
-    bool done = false;
-    AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, x.scalar_type(), "ln_act_bwd_v", [&] {
-      using T = scalar_t;
-      AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, wc.scalar_type(), "ln_act_bwd_v_w", [&] {
-        using TW = scalar_t;
-        constexpr int V = 16 / sizeof(T);
-        int K = 0;
-        if (N > 64 && gys % V == 0) {
-          if (D % (2 * V) == 0 && D / (2 * V) <= 64)
-            K = 2;
-          else if (D % (4 * V) == 0 && D / (4 * V) <= 64)
-            K = 4;
-        }
-        if (K) {
-          // vectorized wave-per-row; bounded blocks keep the per-block
-          // gw/gb atomic flush (blocks x D adds) off the critical path
-          int vblocks = (int)std::min((N + 3) / 4, (long)768);
-          if (silu) {
-            if (K == 2)
-              hipLaunchKernelGGL((ln_act_bwd_v_kernel<T, TW, true, 2>), dim3(vblocks), dim3(kBlock),
-                                 shmem, stream.stream(), (const T*)gy.data_ptr(), (const T*)x.data_ptr(),
-                                 (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
-                                 mean.data_ptr<float>(), rstd.data_ptr<float>(), (T*)gx.data_ptr(),
-                                 gw.data_ptr<float>(), gb.data_ptr<float>(), N, D, gys);
-            else
-              hipLaunchKernelGGL((ln_act_bwd_v_kernel<T, TW, true, 4>), dim3(vblocks), dim3(kBlock),
-                                 shmem, stream.stream(), (const T*)gy.data_ptr(), (const T*)x.data_ptr(),
-                                 (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
-                                 mean.data_ptr<float>(), rstd.data_ptr<float>(), (T*)gx.data_ptr(),
-                                 gw.data_ptr<float>(), gb.data_ptr<float>(), N, D, gys);
-          } else {
-            if (K == 2)
-              hipLaunchKernelGGL((ln_act_bwd_v_kernel<T, TW, false, 2>), dim3(vblocks), dim3(kBlock),
-                                 shmem, stream.stream(), (const T*)gy.data_ptr(), (const T*)x.data_ptr(),
-                                 (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
-                                 mean.data_ptr<float>(), rstd.data_ptr<float>(), (T*)gx.data_ptr(),
-                                 gw.data_ptr<float>(), gb.data_ptr<float>(), N, D, gys);
-            else
-              hipLaunchKernelGGL((ln_act_bwd_v_kernel<T, TW, false, 4>), dim3(vblocks), dim3(kBlock),
-                                 shmem, stream.stream(), (const T*)gy.data_ptr(), (const T*)x.data_ptr(),
-                                 (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
-                                 mean.data_ptr<float>(), rstd.data_ptr<float>(), (T*)gx.data_ptr(),
-                                 gw.data_ptr<float>(), gb.data_ptr<float>(), N, D, gys);
-          }
-          done = true;
-        }
-      });
-    });
-    if (done) return;
-  }
+  const LnRoute r = ln_route(N, D, gys, (int)x.element_size(), true, ln_few_rows());
+  // VEC and ROW: the block's fp32 gw/gb image of one row, after the block_sum scratch
+  const size_t row_shmem = (32 + 2 * (size_t)D) * sizeof(float);
+  if (r.kind == LnRoute::VEC || r.kind == LnRoute::ROW)
+    TORCH_CHECK(row_shmem <= 160 * 1024, "ln_act_bwd: D too large for LDS accumulation");
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, x.scalar_type(), "ln_act_bwd", [&] {
     using T = scalar_t;
     AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, wc.scalar_type(), "ln_act_bwd_w", [&] {
       using TW = scalar_t;
-      if (silu)
-        hipLaunchKernelGGL((ln_act_bwd_kernel<T, TW, true>), dim3(blocks), dim3(kBlock), shmem, stream.stream(),
-                           (const T*)gy.data_ptr(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                           (const TW*)bc.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                           (T*)gx.data_ptr(), gw.data_ptr<float>(), gb.data_ptr<float>(), N, D, gys, N <= 64);
-      else
-        hipLaunchKernelGGL((ln_act_bwd_kernel<T, TW, false>), dim3(blocks), dim3(kBlock), shmem, stream.stream(),
-                           (const T*)gy.data_ptr(), (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
-                           (const TW*)bc.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                           (T*)gx.data_ptr(), gw.data_ptr<float>(), gb.data_ptr<float>(), N, D, gys, N <= 64);
+      with_bool(silu, [&](auto act) {
+        constexpr bool SILU = decltype(act)::value;
+        switch (r.kind) {
+          case LnRoute::CL:
+            launch_ln_bwd_cl<T, TW, SILU>(r.param, N, stream.stream(), (const T*)gy.data_ptr(),
+                                          (const T*)x.data_ptr(), (const TW*)wc.data_ptr(),
+                                          (const TW*)bc.data_ptr(), mean.data_ptr<float>(),
+                                          rstd.data_ptr<float>(), (T*)gx.data_ptr(), gw.data_ptr<float>(),
+                                          gb.data_ptr<float>(), D);
+            break;
+          case LnRoute::SMALL: {
+            const size_t shmem = (size_t)(kBlock >> 6) * 2 * D * sizeof(float);
+            const int blocks = (int)std::min((N + 3) / 4, (long)2048);
+            hipLaunchKernelGGL((ln_act_bwd_small_kernel<T, TW, SILU>), dim3(blocks), dim3(kBlock), shmem,
+                               stream.stream(), (const T*)gy.data_ptr(), (const T*)x.data_ptr(),
+                               (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), mean.data_ptr<float>(),
+                               rstd.data_ptr<float>(), (T*)gx.data_ptr(), gw.data_ptr<float>(),
+                               gb.data_ptr<float>(), N, D, gys);
+            break;
+          }
+          case LnRoute::VEC: {
+            // vectorized wave-per-row; bounded blocks keep the per-block
+            // gw/gb atomic flush (blocks x D adds) off the critical path
+            const int blocks = (int)std::min((N + 3) / 4, (long)768);
+            with_int<2, 4>(r.param, [&](auto loads) {
+              hipLaunchKernelGGL((ln_act_bwd_v_kernel<T, TW, SILU, decltype(loads)::value>), dim3(blocks),
+                                 dim3(kBlock), row_shmem, stream.stream(), (const T*)gy.data_ptr(),
+                                 (const T*)x.data_ptr(), (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
+                                 mean.data_ptr<float>(), rstd.data_ptr<float>(), (T*)gx.data_ptr(),
+                                 gw.data_ptr<float>(), gb.data_ptr<float>(), N, D, gys);
+            });
+            break;
+          }
+          case LnRoute::ROW: {
+            const int blocks = (int)std::min(N, (long)512);
+            hipLaunchKernelGGL((ln_act_bwd_kernel<T, TW, SILU>), dim3(blocks), dim3(kBlock), row_shmem,
+                               stream.stream(), (const T*)gy.data_ptr(), (const T*)x.data_ptr(),
+                               (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), mean.data_ptr<float>(),
+                               rstd.data_ptr<float>(), (T*)gx.data_ptr(), gw.data_ptr<float>(),
+                               gb.data_ptr<float>(), N, D, gys, r.cached);
+            break;
+          }
+        }
+      });
     });
   });
 }
@@ -1566,6 +1509,32 @@ __global__ void __launch_bounds__(kBlock) gru_gates_fwd_vec_kernel(
   }
 }
 
+// Which GRU-gate kernel a [N, 3H] operand takes, both directions:
+//   WIDE (N <= 64 and H >= 2048): few rows x large H leave the chip idle on
+//        the row-per-block kernel; C column chunks so N*C workgroups >= ~384
+//   VEC  (forward only: N > 64, 16-byte-aligned H), then ROW.
+// C is 1 off the WIDE route; cached is the row kernels' N <= 64 argument.
+struct GruRoute {
+  enum Kind { WIDE, VEC, ROW } kind;
+  int C;
+  bool cached;
+};
+GruRoute gru_route(long N, int H, int itemsize, bool backward) {
+  const bool cached = N <= 64;
+  if (N <= 64 && H >= 2048)
+    return {GruRoute::WIDE, std::min<int>(std::max<int>(1, 512 / (int)std::max(N, 1L)), (H + 127) / 128), cached};
+  if (!backward && N > 64 && H % (16 / itemsize) == 0) return {GruRoute::VEC, 1, cached};
+  return {GruRoute::ROW, 1, cached};
+}
+
+// Python-visible query (no device call): (kind, C, cached)
+std::tuple<std::string, int, bool> gru_gates_route(long N, long H, long itemsize, bool backward) {
+  TORCH_CHECK(itemsize == 2 || itemsize == 4 || itemsize == 8, "gru_gates_route: itemsize must be 2, 4 or 8");
+  const GruRoute r = gru_route(N, (int)H, (int)itemsize, backward);
+  static const char* const kNames[] = {"WIDE", "VEC", "ROW"};
+  return {kNames[r.kind], r.C, r.cached};
+}
+
 void gru_gates_fwd_core(const torch::Tensor& y, const torch::Tensor& h, const torch::Tensor& w,
                         const torch::Tensor& b, double eps, torch::Tensor& hout, torch::Tensor& mean,
                         torch::Tensor& rstd, long hs, void* hout2, long h2s, void* hout3 = nullptr,
@@ -1577,32 +1546,34 @@ void gru_gates_fwd_core(const torch::Tensor& y, const torch::Tensor& h, const to
   auto wc = w.contiguous();
   auto bc = b.contiguous();
   auto stream = at::cuda::getCurrentCUDAStream();
-  // wide dispatch: few rows x large H leave the chip idle on the row-per-
-  // block kernel; chunk columns so N*C workgroups >= ~384
-  const bool wide = N <= 64 && H >= 2048;
-  const int C = wide ? std::min<int>(std::max<int>(1, 512 / (int)N), (H + 127) / 128) : 1;
+  const GruRoute r = gru_route(N, H, (int)y.element_size(), false);
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, y.scalar_type(), "gru_gates_fwd", [&] {
     using T = scalar_t;
     AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, wc.scalar_type(), "gru_gates_fwd_w", [&] {
       using TW = scalar_t;
-      if (wide)
-        hipLaunchKernelGGL((gru_gates_fwd_wide_kernel<T, TW>), dim3((int)N, C), dim3(kBlock), 0,
-                           stream.stream(), (const T*)y.data_ptr(), (const T*)h.data_ptr(),
-                           (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), (T*)hout.data_ptr(),
-                           mean.data_ptr<float>(), rstd.data_ptr<float>(), H, (float)eps, hs, (T*)hout2,
-                           h2s, (T*)hout3, h3s);
-      else if (N > 64 && H % (16 / (int)sizeof(T)) == 0)
-        hipLaunchKernelGGL((gru_gates_fwd_vec_kernel<T, TW>), dim3((int)std::min(N, (long)2048)),
-                           dim3(kBlock), 0, stream.stream(), (const T*)y.data_ptr(),
-                           (const T*)h.data_ptr(), (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
-                           (T*)hout.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), N, H,
-                           (float)eps, hs, (T*)hout2, h2s, (T*)hout3, h3s);
-      else
-        hipLaunchKernelGGL((gru_gates_fwd_kernel<T, TW>), dim3((int)N), dim3(kBlock), 0, stream.stream(),
-                           (const T*)y.data_ptr(), (const T*)h.data_ptr(), (const TW*)wc.data_ptr(),
-                           (const TW*)bc.data_ptr(), (T*)hout.data_ptr(), mean.data_ptr<float>(),
-                           rstd.data_ptr<float>(), H, (float)eps, hs, (T*)hout2, h2s, (T*)hout3, h3s,
-                           N <= 64);
+      switch (r.kind) {
+        case GruRoute::WIDE:
+          hipLaunchKernelGGL((gru_gates_fwd_wide_kernel<T, TW>), dim3((int)N, r.C), dim3(kBlock), 0,
+                             stream.stream(), (const T*)y.data_ptr(), (const T*)h.data_ptr(),
+                             (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), (T*)hout.data_ptr(),
+                             mean.data_ptr<float>(), rstd.data_ptr<float>(), H, (float)eps, hs, (T*)hout2,
+                             h2s, (T*)hout3, h3s);
+          break;
+        case GruRoute::VEC:
+          hipLaunchKernelGGL((gru_gates_fwd_vec_kernel<T, TW>), dim3((int)std::min(N, (long)2048)),
+                             dim3(kBlock), 0, stream.stream(), (const T*)y.data_ptr(),
+                             (const T*)h.data_ptr(), (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(),
+                             (T*)hout.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), N, H,
+                             (float)eps, hs, (T*)hout2, h2s, (T*)hout3, h3s);
+          break;
+        case GruRoute::ROW:
+          hipLaunchKernelGGL((gru_gates_fwd_kernel<T, TW>), dim3((int)N), dim3(kBlock), 0, stream.stream(),
+                             (const T*)y.data_ptr(), (const T*)h.data_ptr(), (const TW*)wc.data_ptr(),
+                             (const TW*)bc.data_ptr(), (T*)hout.data_ptr(), mean.data_ptr<float>(),
+                             rstd.data_ptr<float>(), H, (float)eps, hs, (T*)hout2, h2s, (T*)hout3, h3s,
+                             r.cached);
+          break;
+      }
     });
   });
 }
@@ -1928,13 +1899,13 @@ void gru_gates_bwd_core(const torch::Tensor& gh, const void* gh2, const void* gh
   auto wc = w.contiguous();
   auto bc = b.contiguous();
   auto stream = at::cuda::getCurrentCUDAStream();
-  const bool wide = N <= 64 && H >= 2048;
+  const GruRoute r = gru_route(N, H, (int)y.element_size(), true);
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, y.scalar_type(), "gru_gates_bwd", [&] {
     using T = scalar_t;
     AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, wc.scalar_type(), "gru_gates_bwd_w", [&] {
       using TW = scalar_t;
-      if (wide) {
-        const int C = std::min<int>(std::max<int>(1, 512 / (int)N), (H + 127) / 128);
+      if (r.kind == GruRoute::WIDE) {
+        const int C = r.C;
         const int W = (H + C - 1) / C;
         auto spart = torch::empty({N * (long)C * 2}, y.options().dtype(at::kFloat));
         hipLaunchKernelGGL((gru_gates_bwd_stats_kernel<T, TW>), dim3((int)N, C), dim3(kBlock), 0,
@@ -1959,7 +1930,7 @@ void gru_gates_bwd_core(const torch::Tensor& gh, const void* gh2, const void* gh
                          (const T*)y.data_ptr(), (const T*)h.data_ptr(),
                          (const TW*)wc.data_ptr(), (const TW*)bc.data_ptr(), mean.data_ptr<float>(),
                          rstd.data_ptr<float>(), (T*)gy.data_ptr(), (T*)ghprev.data_ptr(), gw.data_ptr<float>(),
-                         gb.data_ptr<float>(), N, H, hs, N <= 64);
+                         gb.data_ptr<float>(), N, H, hs, r.cached);
     });
   });
 }
@@ -2134,16 +2105,6 @@ void adam_step(std::vector<torch::Tensor> params, std::vector<torch::Tensor> gra
 static int wave_row_blocks(long rows) {
   const int waves_per_block = kBlock / 64;
   return (int)((rows + waves_per_block - 1) / waves_per_block);
-}
-
-// runs launch(std::true_type{}) or launch(std::false_type{}): the SAMPLE
-// template argument of the forward kernels
-template <typename F>
-static void with_sample(bool sample, F&& launch) {
-  if (sample)
-    launch(std::true_type{});
-  else
-    launch(std::false_type{});
 }
 
 template <typename T, bool SAMPLE>
@@ -2350,7 +2311,7 @@ static void cat_st_fwd_launch(const torch::Tensor& raw, const float* up, bool sa
   }
   const int blocks = wave_row_blocks(nrows);
   auto stream = at::cuda::getCurrentCUDAStream();
-  with_sample(sample, [&](auto smp) {
+  with_bool(sample, [&](auto smp) {
     hipLaunchKernelGGL((cat_st_fwd_kernel<T, decltype(smp)::value>), dim3(blocks), dim3(kBlock), 0,
                        stream.stream(), (const T*)raw.data_ptr(), up, m.data_ptr<float>(), (T*)onehot.data_ptr(),
                        s.data_ptr<float>(), nrows, K, (float)unimix, ohs, spb, oh2, oh2s);
@@ -2413,12 +2374,6 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-#define SHEEP_CAT_SAMPLE_CASE(GV)                                                                          \
-  case GV:                                                                                                 \
-    hipLaunchKernelGGL((cat_st_sample_kernel<T, GV>), dim3(blocks), dim3(kBlock), 0, stream.stream(),      \
-                       (const T*)raw.data_ptr(), urand.data_ptr<float>(), (T*)onehot.data_ptr(), nrows, K, \
-                       (float)unimix, ohs, spb, (T*)oh2, oh2s);                                            \
-    break;
 void cat_st_sample_o(const torch::Tensor& raw, const torch::Tensor& urand, double unimix, torch::Tensor onehot,
                      const c10::optional<torch::Tensor>& onehot2 = c10::nullopt) {
   CHECK_IN(raw);
@@ -2453,16 +2408,13 @@ void cat_st_sample_o(const torch::Tensor& raw, const torch::Tensor& urand, doubl
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_sample_o", [&] {
     using T = scalar_t;
-    switch (G) {
-      SHEEP_CAT_SAMPLE_CASE(4)
-      SHEEP_CAT_SAMPLE_CASE(8)
-      SHEEP_CAT_SAMPLE_CASE(16)
-      SHEEP_CAT_SAMPLE_CASE(32)
-      SHEEP_CAT_SAMPLE_CASE(64)
-    }
+    with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
+      hipLaunchKernelGGL((cat_st_sample_kernel<T, decltype(group)::value>), dim3(blocks), dim3(kBlock), 0,
+                         stream.stream(), (const T*)raw.data_ptr(), urand.data_ptr<float>(),
+                         (T*)onehot.data_ptr(), nrows, K, (float)unimix, ohs, spb, (T*)oh2, oh2s);
+    });
   });
 }
-#undef SHEEP_CAT_SAMPLE_CASE
 
 // Backward launch shared by cat_st_bwd and cat_st_bwd_o (T = graw's dtype;
 // gon contiguous, gon2 absent or contiguous).
@@ -2616,7 +2568,7 @@ static void cat_st_ragged_launch(const torch::Tensor& raw, const float* up, floa
   const int blocks = wave_row_blocks(waves);
   if (blocks == 0) return;
   auto stream = at::cuda::getCurrentCUDAStream();
-  with_sample(sample, [&](auto smp) {
+  with_bool(sample, [&](auto smp) {
     hipLaunchKernelGGL((cat_st_ragged_fwd_kernel<T, decltype(smp)::value>), dim3(blocks), dim3(kBlock), 0,
                        stream.stream(), (const T*)raw.data_ptr(), up, m, oh, s, nrows, A, heads, (float)unimix,
                        ohs, oh2, oh2s);
@@ -2761,13 +2713,12 @@ torch::Tensor masked_lerp_fwd(const torch::Tensor& x, const c10::optional<torch:
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, x.scalar_type(), "masked_lerp_fwd", [&] {
     using T = scalar_t;
-    if (init.has_value())
-      hipLaunchKernelGGL((masked_lerp_fwd_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                         (const T*)x.data_ptr(), (const T*)init->data_ptr(), (const T*)f.data_ptr(),
-                         (T*)y.data_ptr(), rows, cols);
-    else
-      hipLaunchKernelGGL((masked_lerp_fwd_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                         (const T*)x.data_ptr(), nullptr, (const T*)f.data_ptr(), (T*)y.data_ptr(), rows, cols);
+    const T* ip = init.has_value() ? (const T*)init->data_ptr() : nullptr;
+    with_bool(init.has_value(), [&](auto has_init) {
+      hipLaunchKernelGGL((masked_lerp_fwd_kernel<T, decltype(has_init)::value>), dim3(blocks), dim3(kBlock), 0,
+                         stream.stream(), (const T*)x.data_ptr(), ip, (const T*)f.data_ptr(), (T*)y.data_ptr(),
+                         rows, cols);
+    });
   });
   return y;
 }
@@ -2782,13 +2733,12 @@ std::vector<torch::Tensor> masked_lerp_bwd(const torch::Tensor& g, const torch::
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, g.scalar_type(), "masked_lerp_bwd", [&] {
     using T = scalar_t;
-    if (has_init)
-      hipLaunchKernelGGL((masked_lerp_bwd_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                         (const T*)g.data_ptr(), (const T*)f.data_ptr(), (T*)gx.data_ptr(), (T*)ginit.data_ptr(),
+    T* gip = has_init ? (T*)ginit.data_ptr() : nullptr;
+    with_bool(has_init, [&](auto init) {
+      hipLaunchKernelGGL((masked_lerp_bwd_kernel<T, decltype(init)::value>), dim3(blocks), dim3(kBlock), 0,
+                         stream.stream(), (const T*)g.data_ptr(), (const T*)f.data_ptr(), (T*)gx.data_ptr(), gip,
                          rows, cols);
-    else
-      hipLaunchKernelGGL((masked_lerp_bwd_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                         (const T*)g.data_ptr(), (const T*)f.data_ptr(), (T*)gx.data_ptr(), nullptr, rows, cols);
+    });
   });
   return {gx, ginit};
 }
@@ -3381,16 +3331,13 @@ void scan_resets_fwd(const torch::Tensor& z_prev, const torch::Tensor& iz, const
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, actions.scalar_type(), "scan_resets_fwd", [&] {
     using T = scalar_t;
-    if (t0)
-      hipLaunchKernelGGL((scan_resets_fwd_kernel<T, true>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                         (const T*)z_prev.data_ptr(), (const T*)iz.data_ptr(), (const T*)h_prev.data_ptr(),
-                         (const T*)ih.data_ptr(), (const T*)actions.data_ptr(), (const T*)f.data_ptr(),
-                         (T*)x.data_ptr(), x.stride(0), (T*)hu.data_ptr(), hu.stride(0), B, SK, A, H);
-    else
-      hipLaunchKernelGGL((scan_resets_fwd_kernel<T, false>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                         (const T*)z_prev.data_ptr(), (const T*)iz.data_ptr(), (const T*)h_prev.data_ptr(),
-                         (const T*)ih.data_ptr(), (const T*)actions.data_ptr(), (const T*)f.data_ptr(),
-                         (T*)x.data_ptr(), x.stride(0), (T*)hu.data_ptr(), hu.stride(0), B, SK, A, H);
+    with_bool(t0, [&](auto first) {
+      hipLaunchKernelGGL((scan_resets_fwd_kernel<T, decltype(first)::value>), dim3(blocks), dim3(kBlock), 0,
+                         stream.stream(), (const T*)z_prev.data_ptr(), (const T*)iz.data_ptr(),
+                         (const T*)h_prev.data_ptr(), (const T*)ih.data_ptr(), (const T*)actions.data_ptr(),
+                         (const T*)f.data_ptr(), (T*)x.data_ptr(), x.stride(0), (T*)hu.data_ptr(), hu.stride(0),
+                         B, SK, A, H);
+    });
   });
 }
 
@@ -3726,24 +3673,15 @@ void g16_ln_silu(const torch::Tensor& A, const torch::Tensor& W, const torch::Te
   int B = (int)A.size(0), K = (int)A.size(1), N = (int)W.size(0);
   TORCH_CHECK(B <= 16 && N % 64 == 0 && N <= 512 && G.stride(1) == 1 && Y.stride(1) == 1);
   auto stream = at::cuda::getCurrentCUDAStream();
-#define SHEEP_G16LN_CASE(TV)                                                                              \
-  case TV:                                                                                                \
-    hipLaunchKernelGGL(g16_ln_silu_kernel<TV>, dim3(1), dim3(256), 16 * N * sizeof(float),                \
-                       stream.stream(), (const __hip_bfloat16*)A.data_ptr(), A.stride(0),                 \
-                       (const __hip_bfloat16*)W.data_ptr(), (const __hip_bfloat16*)lnw.data_ptr(),        \
-                       (const __hip_bfloat16*)lnb.data_ptr(), (__hip_bfloat16*)G.data_ptr(), G.stride(0), \
-                       (__hip_bfloat16*)Y.data_ptr(), Y.stride(0), mean.data_ptr<float>(),                \
-                       rstd.data_ptr<float>(), B, N, K, (float)eps);                                      \
-    break;
-  switch (N / 64) {
-    SHEEP_G16LN_CASE(1)
-    SHEEP_G16LN_CASE(2)
-    SHEEP_G16LN_CASE(4)
-    SHEEP_G16LN_CASE(8)
-    default:
-      TORCH_CHECK(false, "g16_ln_silu: unsupported N");
-  }
-#undef SHEEP_G16LN_CASE
+  const bool ok = with_int<1, 2, 4, 8>(N / 64, [&](auto tiles) {
+    hipLaunchKernelGGL((g16_ln_silu_kernel<decltype(tiles)::value>), dim3(1), dim3(256), 16 * N * sizeof(float),
+                       stream.stream(), (const __hip_bfloat16*)A.data_ptr(), A.stride(0),
+                       (const __hip_bfloat16*)W.data_ptr(), (const __hip_bfloat16*)lnw.data_ptr(),
+                       (const __hip_bfloat16*)lnb.data_ptr(), (__hip_bfloat16*)G.data_ptr(), G.stride(0),
+                       (__hip_bfloat16*)Y.data_ptr(), Y.stride(0), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), B, N, K, (float)eps);
+  });
+  TORCH_CHECK(ok, "g16_ln_silu: unsupported N");
 }
 
 // single-workgroup GEMM + bias + unimix categorical-ST epilogue (the
@@ -3816,24 +3754,14 @@ void g16_cat_st(const torch::Tensor& A, const torch::Tensor& W, const torch::Ten
   TORCH_CHECK(B <= 16 && N % 64 == 0 && N <= 1024 && m.is_contiguous() && z.is_contiguous() &&
               s.is_contiguous() && N % KD == 0);
   auto stream = at::cuda::getCurrentCUDAStream();
-#define SHEEP_G16CS_CASE(TV)                                                                             \
-  case TV:                                                                                               \
-    hipLaunchKernelGGL(g16_cat_st_kernel<TV>, dim3(1), dim3(256), 16 * N * sizeof(float),                \
-                       stream.stream(), (const __hip_bfloat16*)A.data_ptr(), A.stride(0),                \
-                       (const __hip_bfloat16*)W.data_ptr(), (const __hip_bfloat16*)bias.data_ptr(),      \
-                       urand.data_ptr<float>(), m.data_ptr<float>(), (__hip_bfloat16*)z.data_ptr(),      \
-                       s.data_ptr<float>(), B, N, K, (int)KD, (float)unimix);                            \
-    break;
-  switch (N / 64) {
-    SHEEP_G16CS_CASE(1)
-    SHEEP_G16CS_CASE(2)
-    SHEEP_G16CS_CASE(4)
-    SHEEP_G16CS_CASE(8)
-    SHEEP_G16CS_CASE(16)
-    default:
-      TORCH_CHECK(false, "g16_cat_st: unsupported N");
-  }
-#undef SHEEP_G16CS_CASE
+  const bool ok = with_int<1, 2, 4, 8, 16>(N / 64, [&](auto tiles) {
+    hipLaunchKernelGGL((g16_cat_st_kernel<decltype(tiles)::value>), dim3(1), dim3(256), 16 * N * sizeof(float),
+                       stream.stream(), (const __hip_bfloat16*)A.data_ptr(), A.stride(0),
+                       (const __hip_bfloat16*)W.data_ptr(), (const __hip_bfloat16*)bias.data_ptr(),
+                       urand.data_ptr<float>(), m.data_ptr<float>(), (__hip_bfloat16*)z.data_ptr(),
+                       s.data_ptr<float>(), B, N, K, (int)KD, (float)unimix);
+  });
+  TORCH_CHECK(ok, "g16_cat_st: unsupported N");
 }
 
 // Micro-kernel used by the layout unit test: Y[16,N] = X[16,K] @ W[N,K]^T.
@@ -5687,18 +5615,11 @@ void replay_gather(const torch::Tensor& ptrs, const torch::Tensor& starts, torch
   const long total = S * L * (row_bytes / unit);
   int blocks = (int)std::min((total + kBlock - 1) / kBlock, (long)2048);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (unit == 16)
-    hipLaunchKernelGGL(replay_gather_kernel<16>, dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                       ptrs.data_ptr<long>(), starts.data_ptr<long>(), (unsigned char*)out.data_ptr(),
-                       S, L, cap, row_bytes);
-  else if (unit == 4)
-    hipLaunchKernelGGL(replay_gather_kernel<4>, dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                       ptrs.data_ptr<long>(), starts.data_ptr<long>(), (unsigned char*)out.data_ptr(),
-                       S, L, cap, row_bytes);
-  else
-    hipLaunchKernelGGL(replay_gather_kernel<1>, dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                       ptrs.data_ptr<long>(), starts.data_ptr<long>(), (unsigned char*)out.data_ptr(),
-                       S, L, cap, row_bytes);
+  with_int<16, 4, 1>(unit, [&](auto bytes) {
+    hipLaunchKernelGGL((replay_gather_kernel<decltype(bytes)::value>), dim3(blocks), dim3(kBlock), 0,
+                       stream.stream(), ptrs.data_ptr<long>(), starts.data_ptr<long>(),
+                       (unsigned char*)out.data_ptr(), S, L, cap, row_bytes);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -5843,19 +5764,14 @@ void scan3_f1(const c10::optional<torch::Tensor>& z_prev, const torch::Tensor& i
   const bool t0 = !z_prev.has_value();
   const __hip_bfloat16* zp = t0 ? nullptr : s3_bp(*z_prev);
   const __hip_bfloat16* hp = h_prev.has_value() ? s3_bp(*h_prev) : nullptr;
-#define S3_F1(T0V)                                                                                     \
-  hipLaunchKernelGGL((scan3_lnsilu_kernel<true, T0V>), dim3(ntiles, KS), dim3(256), 0,                 \
-                     stream.stream(), zp, 0, s3_bp(iz), hp, s3_bp(ih), s3_bp(act), s3_bp(f),           \
-                     s3_bp(W1), s3_bp(lnw), s3_bp(lnb), s3_bpm(x_out), x_out.stride(0),                \
-                     s3_bpm(hu_out), hu_out.stride(0), s3_bpm(g_out), g_out.stride(0),                 \
-                     mean.data_ptr<float>(), rstd.data_ptr<float>(), scratch.data_ptr<float>(),        \
-                     tickets.data_ptr<int>(), ticket2.data_ptr<int>(), ws2.data_ptr<float>(), B, SK,   \
-                     A, H, N, K, (float)eps, H, (int)gen)
-  if (t0)
-    S3_F1(true);
-  else
-    S3_F1(false);
-#undef S3_F1
+  with_bool(t0, [&](auto first) {
+    hipLaunchKernelGGL((scan3_lnsilu_kernel<true, decltype(first)::value>), dim3(ntiles, KS), dim3(256), 0,
+                       stream.stream(), zp, 0, s3_bp(iz), hp, s3_bp(ih), s3_bp(act), s3_bp(f), s3_bp(W1),
+                       s3_bp(lnw), s3_bp(lnb), s3_bpm(x_out), x_out.stride(0), s3_bpm(hu_out), hu_out.stride(0),
+                       s3_bpm(g_out), g_out.stride(0), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       scratch.data_ptr<float>(), tickets.data_ptr<int>(), ticket2.data_ptr<int>(),
+                       ws2.data_ptr<float>(), B, SK, A, H, N, K, (float)eps, H, (int)gen);
+  });
 }
 
 void scan3_f3(const torch::Tensor& a_in, const torch::Tensor& W3, const torch::Tensor& lnw,
@@ -6277,6 +6193,9 @@ __global__ void nll_bwd_kernel(const float* __restrict__ g, const T* __restrict_
   }
 }
 
+// any mode other than 0 and 1 is the Bernoulli one
+static int nll_mode(long mode) { return mode == 0 || mode == 1 ? (int)mode : 2; }
+
 torch::Tensor nll_fwd(const torch::Tensor& pred, const torch::Tensor& tgt, long D, long mode) {
   CHECK_IN(pred);
   TORCH_CHECK(tgt.is_contiguous() && tgt.scalar_type() == at::kFloat && tgt.numel() == pred.numel());
@@ -6287,19 +6206,11 @@ torch::Tensor nll_fwd(const torch::Tensor& pred, const torch::Tensor& tgt, long 
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pred.scalar_type(), "nll_fwd", [&] {
     using T = scalar_t;
-    switch (mode) {
-      case 0:
-        hipLaunchKernelGGL((nll_fwd_kernel<T, 0>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                           (const T*)pred.data_ptr(), tgt.data_ptr<float>(), out.data_ptr<float>(), R, D);
-        break;
-      case 1:
-        hipLaunchKernelGGL((nll_fwd_kernel<T, 1>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                           (const T*)pred.data_ptr(), tgt.data_ptr<float>(), out.data_ptr<float>(), R, D);
-        break;
-      default:
-        hipLaunchKernelGGL((nll_fwd_kernel<T, 2>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                           (const T*)pred.data_ptr(), tgt.data_ptr<float>(), out.data_ptr<float>(), R, D);
-    }
+    with_int<0, 1, 2>(nll_mode(mode), [&](auto md) {
+      hipLaunchKernelGGL((nll_fwd_kernel<T, decltype(md)::value>), dim3(blocks), dim3(kBlock), 0,
+                         stream.stream(), (const T*)pred.data_ptr(), tgt.data_ptr<float>(), out.data_ptr<float>(),
+                         R, D);
+    });
   });
   return out;
 }
@@ -6315,22 +6226,11 @@ torch::Tensor nll_bwd(const torch::Tensor& g, const torch::Tensor& pred, const t
   auto stream = at::cuda::getCurrentCUDAStream();
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pred.scalar_type(), "nll_bwd", [&] {
     using T = scalar_t;
-    switch (mode) {
-      case 0:
-        hipLaunchKernelGGL((nll_bwd_kernel<T, 0>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                           g.data_ptr<float>(), (const T*)pred.data_ptr(), tgt.data_ptr<float>(),
-                           (T*)gpred.data_ptr(), R, D);
-        break;
-      case 1:
-        hipLaunchKernelGGL((nll_bwd_kernel<T, 1>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                           g.data_ptr<float>(), (const T*)pred.data_ptr(), tgt.data_ptr<float>(),
-                           (T*)gpred.data_ptr(), R, D);
-        break;
-      default:
-        hipLaunchKernelGGL((nll_bwd_kernel<T, 2>), dim3(blocks), dim3(kBlock), 0, stream.stream(),
-                           g.data_ptr<float>(), (const T*)pred.data_ptr(), tgt.data_ptr<float>(),
-                           (T*)gpred.data_ptr(), R, D);
-    }
+    with_int<0, 1, 2>(nll_mode(mode), [&](auto md) {
+      hipLaunchKernelGGL((nll_bwd_kernel<T, decltype(md)::value>), dim3(blocks), dim3(kBlock), 0,
+                         stream.stream(), g.data_ptr<float>(), (const T*)pred.data_ptr(), tgt.data_ptr<float>(),
+                         (T*)gpred.data_ptr(), R, D);
+    });
   });
   return gpred;
 }
@@ -6359,19 +6259,14 @@ void scan2_f1(const c10::optional<torch::Tensor>& z_prev, const torch::Tensor& i
   const bool t0 = !z_prev.has_value();
   const __hip_bfloat16* zp = t0 ? nullptr : sc2_bp(*z_prev);
   const __hip_bfloat16* hp = h_prev.has_value() ? sc2_bp(*h_prev) : nullptr;
-#define SC2_F1_LAUNCH(T0V)                                                                            \
-  hipLaunchKernelGGL((scan2_lnsilu_kernel<true, T0V, false>), dim3(N / 64), dim3(256), shmem,         \
-                     stream.stream(),                                                                 \
-                     zp, 0, sc2_bp(iz), hp, sc2_bp(ih), sc2_bp(act), sc2_bp(f), sc2_bp(W1),           \
-                     sc2_bp(lnw), sc2_bp(lnb), sc2_bpm(x_out), x_out.stride(0), sc2_bpm(hu_out),      \
-                     hu_out.stride(0), sc2_bpm(g_out), g_out.stride(0), mean.data_ptr<float>(),       \
-                     rstd.data_ptr<float>(), ws2.data_ptr<float>(), ticket.data_ptr<int>(), B, SK, A, \
-                     H, N, K, (float)eps, H)
-  if (t0)
-    SC2_F1_LAUNCH(true);
-  else
-    SC2_F1_LAUNCH(false);
-#undef SC2_F1_LAUNCH
+  with_bool(t0, [&](auto first) {
+    hipLaunchKernelGGL((scan2_lnsilu_kernel<true, decltype(first)::value, false>), dim3(N / 64), dim3(256), shmem,
+                       stream.stream(), zp, 0, sc2_bp(iz), hp, sc2_bp(ih), sc2_bp(act), sc2_bp(f), sc2_bp(W1),
+                       sc2_bp(lnw), sc2_bp(lnb), sc2_bpm(x_out), x_out.stride(0), sc2_bpm(hu_out),
+                       hu_out.stride(0), sc2_bpm(g_out), g_out.stride(0), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), ws2.data_ptr<float>(), ticket.data_ptr<int>(), B, SK, A, H, N, K,
+                       (float)eps, H);
+  });
 }
 
 void scan2_f3(const torch::Tensor& a_in, const torch::Tensor& W3, const torch::Tensor& lnw,
@@ -6389,20 +6284,14 @@ void scan2_f3(const torch::Tensor& a_in, const torch::Tensor& W3, const torch::T
                               : ((16 * KP * 2 + 15) & ~15) + 32 * sizeof(float);
   TORCH_CHECK(shmem <= 160 * 1024, "scan2_f3: K too large for LDS");
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (ksplit)
-    hipLaunchKernelGGL((scan2_lnsilu_kernel<false, false, true>), dim3(N / 16), dim3(256), shmem,
-                       stream.stream(),
+  with_bool(ksplit, [&](auto split) {
+    hipLaunchKernelGGL((scan2_lnsilu_kernel<false, false, decltype(split)::value>),
+                       dim3(N / (ksplit ? 16 : 64)), dim3(256), shmem, stream.stream(),
                        sc2_bp(a_in), a_in.stride(0), nullptr, nullptr, nullptr, nullptr, nullptr,
                        sc2_bp(W3), sc2_bp(lnw), sc2_bp(lnb), nullptr, 0, sc2_bpm(p_out), p_out.stride(0),
                        sc2_bpm(g_out), g_out.stride(0), mean.data_ptr<float>(), rstd.data_ptr<float>(),
                        ws2.data_ptr<float>(), ticket.data_ptr<int>(), B, 0, 0, 0, N, K, (float)eps, 0);
-  else
-    hipLaunchKernelGGL((scan2_lnsilu_kernel<false, false, false>), dim3(N / 64), dim3(256), shmem,
-                       stream.stream(),
-                       sc2_bp(a_in), a_in.stride(0), nullptr, nullptr, nullptr, nullptr, nullptr,
-                       sc2_bp(W3), sc2_bp(lnw), sc2_bp(lnb), nullptr, 0, sc2_bpm(p_out), p_out.stride(0),
-                       sc2_bpm(g_out), g_out.stride(0), mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       ws2.data_ptr<float>(), ticket.data_ptr<int>(), B, 0, 0, 0, N, K, (float)eps, 0);
+  });
 }
 
 void scan2_f2(const torch::Tensor& hu, const torch::Tensor& W2, const torch::Tensor& lnw,
@@ -6845,6 +6734,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_act_bwd", &ln_act_bwd);
   m.def("gru_gates_fwd", &gru_gates_fwd);
   m.def("gru_gates_bwd", &gru_gates_bwd);
+  m.def("ln_act_route", &ln_act_route, py::arg("N"), py::arg("D"), py::arg("stride"), py::arg("itemsize"),
+        py::arg("backward"), py::arg("few_rows") = -1);
+  m.def("gru_gates_route", &gru_gates_route, py::arg("N"), py::arg("H"), py::arg("itemsize"),
+        py::arg("backward"));
   m.def("gae_scan", &gae_scan);
   m.def("lambda_scan_fwd", &lambda_scan_fwd);
   m.def("lambda_scan_bwd", &lambda_scan_bwd);

@@ -1102,9 +1102,12 @@ def test_ppo_losses_fused_matches_eager(clip_vloss, reduction):
 @requires_gpu
 @pytest.mark.parametrize("D", [640, 768, 1024, 1536, 2048])
 def test_ln_act_large_row_count(D):
-    """Behaviour-MLP shapes (many rows x 512<D<=2048): the vectorized
-    wave-per-row path must stay numerically identical, including partial
-    lane coverage (D=640/768) and K=4 rows (D=1536/2048)."""
+    """Behaviour-MLP shapes (many rows x 512<D<=2048) in fp32, where a lane
+    loads 4 elements: D=640/768/1024 take the vectorized wave-per-row
+    kernels with K=4 (40, 48 and 64 of 64 lanes); D=1536/2048 would need 96
+    and 128 lanes and take the block-per-row kernels, uncached.  The bf16
+    K=4 shape is test_gpu_ln_few_rows.test_ln_wide_rows_k4;
+    test_kernel_routes pins all of these routes."""
     torch.manual_seed(7)
     N = 16384 if D == 1024 else 4096
     x = torch.randn(N, D)

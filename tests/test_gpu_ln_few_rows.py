@@ -2,7 +2,9 @@
 row-strided operands must give the same results whichever kernel the host
 dispatch picks (N = 64 / 65 straddle the backward's default few-row limit;
 the forward routes by stride alone), and the ``*_acc`` backward adds to its
-fp32 accumulators instead of overwriting them.
+fp32 accumulators instead of overwriting them.  test_ln_wide_rows_k4 runs
+the same checks at N=65, D=1536, the one shape here that reaches the bf16
+K=4 vectorized kernels, and asserts that route first.
 
 Reference: float64 on the same quantized inputs; bounds are test_ln_act's for
 the dtype (forward 1e-5 / 3e-2, gx 1e-4 / 1e-1, gw/gb atol 1e-3 / 0.3 with
@@ -48,7 +50,29 @@ def _ref(x, w, b, gy, silu):
 def test_ln_few_rows(N, D, dtype, silu):
     from sheeprl_amd.ops._ext import require_ext
 
+    _check(require_ext(), N, D, dtype, silu)
+
+
+@requires_gpu
+@pytest.mark.parametrize("silu", [True, False])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_ln_wide_rows_k4(dtype, silu):
+    """N=65, D=1536: in bf16 the vectorized wave-per-row kernels with K=4
+    (48 of 64 lanes active), forward and backward, contiguous and row-strided;
+    in fp32 (96 lanes would be needed) the block-per-row kernels, uncached."""
+    from sheeprl_amd.ops._ext import require_ext
+
     ext = require_ext()
+    N, D = 65, 1536
+    itemsize = torch.empty((), dtype=dtype).element_size()
+    want = ("VEC", 4, False) if dtype == torch.bfloat16 else ("ROW", 0, False)
+    # the strides _check runs: contiguous, forward slice of [N, D+24], backward slice of [N, 8+D]
+    for backward, stride in ((False, D), (False, D + 24), (True, D), (True, 8 + D)):
+        assert tuple(ext.ln_act_route(N, D, stride, itemsize, backward)) == want, (backward, stride)
+    _check(ext, N, D, dtype, silu)
+
+
+def _check(ext, N, D, dtype, silu):
     torch.manual_seed(N * 1000 + D)
     dev = "cuda"
     x = torch.randn(N, D, device=dev).to(dtype)
@@ -77,7 +101,7 @@ def test_ln_few_rows(N, D, dtype, silu):
     assert torch.allclose(stats[False][0].double(), xd.mean(-1), atol=1e-5, rtol=1e-5)
     assert torch.allclose(stats[False][1].double(), torch.rsqrt(xd.var(-1, unbiased=False) + EPS),
                           atol=1e-5, rtol=1e-4)
-    # (fp32 sums of D <= 512 unit-scale terms: ~D * 2^-24 worst case, in any order)
+    # (fp32 sums of D <= 1536 unit-scale terms, divided by D: ~2^-24 * sqrt(D) in any order)
     assert torch.allclose(stats[True][0], stats[False][0], atol=1e-5, rtol=1e-5)
     assert torch.allclose(stats[True][1], stats[False][1], atol=1e-5, rtol=1e-4)
 
