@@ -14,6 +14,7 @@ state sampling stays in fp32 for categorical stability under bf16-true.
 from __future__ import annotations
 
 import copy
+import os
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -23,7 +24,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from sheeprl_amd import ops
-from sheeprl_amd.distributions import OneHotCategoricalST, unimix_logits
+from sheeprl_amd.distributions import FusedContinuousDist, OneHotCategoricalST, unimix_logits
 from sheeprl_amd.envs import spaces
 from sheeprl_amd.models import (
     FastLinear,
@@ -471,19 +472,17 @@ class Actor(nn.Module):
     ) -> Tuple[Tuple[Tensor, ...], Tuple[td.Distribution, ...]]:
         out = self.model(state)
         pre_dist = [head(out) for head in self.mlp_heads]
+        if self.is_continuous and not greedy and self._fused_cont_head(pre_dist[0]):
+            # fused sample + clip + entropy (ops.continuous_actor_head); one
+            # randn per forward, so the draw is safe under graph capture
+            pre = pre_dist[0]
+            eps = torch.randn(*pre.shape[:-1], pre.shape[-1] // 2, dtype=torch.float32, device=pre.device)
+            actions, entropy = ops.continuous_actor_head(
+                pre, eps, self.distribution, self.init_std, self.min_std, self.max_std, self._action_clip
+            )
+            return (actions,), (FusedContinuousDist(entropy, lambda: self._continuous_dist(pre)),)
         if self.is_continuous:
-            mean, std = torch.chunk(pre_dist[0].float(), 2, -1)
-            if self.distribution == "tanh_normal":
-                mean = 5 * torch.tanh(mean / 5)
-                std = F.softplus(std + self.init_std) + self.min_std
-                dist = td.Independent(
-                    td.TransformedDistribution(td.Normal(mean, std), td.TanhTransform()), 1
-                )
-            elif self.distribution == "normal":
-                dist = td.Independent(td.Normal(mean, std), 1)
-            else:  # scaled_normal
-                std = (self.max_std - self.min_std) * torch.sigmoid(std + self.init_std) + self.min_std
-                dist = td.Independent(td.Normal(torch.tanh(mean), std), 1)
+            dist = self._continuous_dist(pre_dist[0])
             if not greedy:
                 actions = dist.rsample()
             else:
@@ -505,6 +504,28 @@ class Actor(nn.Module):
             dists.append(LogProbCategorical(m))
             actions_list.append(onehot)
         return tuple(actions_list), tuple(dists)
+
+    def _fused_cont_head(self, pre: Tensor) -> bool:
+        """Whether a sampling forward takes ops.continuous_actor_head
+        (SHEEPRL_AMD_CONT_HEAD=0 puts the torch chain back)."""
+        return (
+            self.distribution in ("scaled_normal", "tanh_normal")
+            and ops.use_hip(pre)
+            and os.environ.get("SHEEPRL_AMD_CONT_HEAD", "1") == "1"
+        )
+
+    def _continuous_dist(self, pre: Tensor) -> td.Distribution:
+        """The torch distribution of a continuous head's output [..., 2A]."""
+        mean, std = torch.chunk(pre.float(), 2, -1)
+        if self.distribution == "tanh_normal":
+            mean = 5 * torch.tanh(mean / 5)
+            std = F.softplus(std + self.init_std) + self.min_std
+            return td.Independent(td.TransformedDistribution(td.Normal(mean, std), td.TanhTransform()), 1)
+        if self.distribution == "normal":
+            return td.Independent(td.Normal(mean, std), 1)
+        # scaled_normal
+        std = (self.max_std - self.min_std) * torch.sigmoid(std + self.init_std) + self.min_std
+        return td.Independent(td.Normal(torch.tanh(mean), std), 1)
 
     def policy_log_probs(self, state: Tensor) -> Tensor:
         """Normalized (unimix) log-probs of every discrete head, concatenated

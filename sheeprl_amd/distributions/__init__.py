@@ -1,5 +1,6 @@
 from sheeprl_amd.distributions.dists import (
     LogProbCategorical,
+    FusedContinuousDist,
     BernoulliSafeMode,
     MSEDistribution,
     OneHotCategoricalST,
@@ -20,4 +21,5 @@ __all__ = [
     "TanhNormal",
     "unimix_logits",
     "LogProbCategorical",
+    "FusedContinuousDist",
 ]

@@ -202,6 +202,32 @@ class LogProbCategorical:
         return torch.nn.functional.one_hot(idx, self.logits.shape[-1]).to(self.logits.dtype)
 
 
+class FusedContinuousDist:
+    """What the fused continuous actor head (``ops.continuous_actor_head``)
+    returns in place of a ``td`` distribution: ``entropy()`` is the kernel's
+    per-row value (``None`` stands for tanh_normal, which has no closed form);
+    every other attribute comes from the ``td`` distribution the torch path
+    would have built, constructed by ``build()`` on first use."""
+
+    def __init__(self, entropy: Optional[Tensor], build) -> None:
+        self._entropy = entropy
+        self._build = build
+        self._dist = None
+
+    def entropy(self) -> Tensor:
+        if self._entropy is None:
+            raise NotImplementedError("tanh_normal has no closed-form entropy")
+        return self._entropy
+
+    def __getattr__(self, name: str):
+        # reached only for what the instance does not define itself
+        if name.startswith("_"):
+            raise AttributeError(name)
+        if self._dist is None:
+            self._dist = self._build()
+        return getattr(self._dist, name)
+
+
 class BernoulliSafeMode(td.Bernoulli):
     """Bernoulli whose mode is well-defined at p=0.5 (reference :409-416)."""
 

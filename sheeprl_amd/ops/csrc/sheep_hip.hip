@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <climits>
 #include <string>
 #include <tuple>
 #include <type_traits>
@@ -6586,6 +6587,235 @@ std::vector<torch::Tensor> tanh_normal_bwd(const torch::Tensor& gaction, const t
 }
 
 // ---------------------------------------------------------------------------
+// Fused continuous actor head of the Dreamer family (dreamer_v3/agent.py
+// Actor.forward, Box action spaces): reparameterized sample, action clip and
+// per-row entropy in one kernel each way, from the head GEMM's output
+// pre = [N, 2A] (columns [0, A) mean logits a, [A, 2A) std logits b) and
+// standard normal noise eps [N, A].
+//   scaled_normal: mu = tanh(a), sd = (max_std-min_std)*sigmoid(b+init_std)+min_std,
+//                  x = mu + sd*eps, entropy = sum_j (0.5 + 0.5*log(2pi) + log sd_j)
+//   tanh_normal  : mu = 5*tanh(a/5), sd = softplus(b+init_std)+min_std,
+//                  x = tanh(mu + sd*eps), no entropy
+//   clip > 0     : y = x*f, f = clip/max(clip, |x|) a constant for the gradient
+// Many rows, very short rows: a row owns an aligned group of G lanes (G = next
+// power of two >= A, 4..64), so 64/G rows share a wave and a block covers
+// 4*64/G rows.  Lane j loads a_j and b_j of its row (two coalesced streams A
+// apart), keeps both columns' math in registers and stores y_j; the entropy is
+// a G-lane butterfly whose idle lanes hold 0.  A > 64 is the G = 64 kernel,
+// one wave per row, with the column loop taken more than once.  Backward
+// saves nothing but pre and eps and recomputes the rest.
+// ---------------------------------------------------------------------------
+
+// The two kernels below are built without packed-fp32 instructions (libm's
+// tanhf/log1pf expansions otherwise pair their polynomial steps into them).
+#define NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
+
+template <typename T>
+__device__ __forceinline__ float tsigmoid(float z) {
+  return 1.f / (1.f + texp<T>(-z));
+}
+
+// One column of the head: everything the forward stores and the backward
+// needs, from (a, b, eps).  T picks libm (fp32) or the fast transcendentals.
+struct ContHeadCol {
+  float x;    // unclipped action
+  float f;    // clip factor
+  float sd;   // standard deviation
+  float dxa;  // dx/da
+  float dsb;  // d sd/db
+  float dxs;  // dx/d sd
+};
+template <typename T, bool TANH>
+__device__ __forceinline__ ContHeadCol cont_head_col(float a, float b, float e, float init_std, float min_std,
+                                                     float max_std, float clip) {
+  ContHeadCol c;
+  const float z = b + init_std;
+  if constexpr (TANH) {
+    const float t = ttanh<T>(a * 0.2f);
+    // overflow-safe softplus: max(z, 0) + log(1 + exp(-|z|))
+    float sp;
+    if constexpr (sizeof(T) == 2)
+      sp = fmaxf(z, 0.f) + __logf(1.f + __expf(-fabsf(z)));
+    else
+      sp = fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
+    c.sd = sp + min_std;
+    c.x = ttanh<T>(5.f * t + c.sd * e);
+    const float du = 1.f - c.x * c.x;
+    c.dxa = du * (1.f - t * t);
+    c.dsb = tsigmoid<T>(z);
+    c.dxs = du * e;
+  } else {
+    const float mu = ttanh<T>(a);
+    const float s = tsigmoid<T>(z);
+    c.sd = (max_std - min_std) * s + min_std;
+    c.x = mu + c.sd * e;
+    c.dxa = 1.f - mu * mu;
+    c.dsb = (max_std - min_std) * s * (1.f - s);
+    c.dxs = e;
+  }
+  c.f = clip > 0.f ? clip / fmaxf(clip, fabsf(c.x)) : 1.f;
+  return c;
+}
+
+template <typename T, int G, bool TANH>
+__global__ void __launch_bounds__(256) NO_PACKED_FP32
+    cont_head_fwd_kernel(const T* __restrict__ pre, const float* __restrict__ eps, T* __restrict__ act,
+                         float* __restrict__ ent, long N, int A, float init_std, float min_std, float max_std,
+                         float clip) {
+  const int lane = threadIdx.x & (G - 1);
+  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  // groups past the last row recompute it and store nothing: every lane of
+  // the wave stays in the shuffles
+  const bool live = row < N;
+  if (!live) row = N - 1;
+  const T* pr = pre + row * 2L * A;
+  const float* er = eps + row * (long)A;
+  T* yr = act + row * (long)A;
+  float h = 0.f;
+  for (int j = lane; j < A; j += G) {
+    const ContHeadCol c =
+        cont_head_col<T, TANH>(ld(pr, j), ld(pr, A + j), er[j], init_std, min_std, max_std, clip);
+    // x*f can land one ulp outside [-clip, clip]; |f| = 1 leaves x as it is
+    float y = c.x * c.f;
+    if (c.f < 1.f) y = fminf(fmaxf(y, -clip), clip);
+    if (live) st(yr, j, y);
+    if constexpr (!TANH) h += 1.4189385332046727f + tlog<T>(c.sd);  // 0.5 + 0.5*log(2pi)
+  }
+  if constexpr (!TANH) {
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) h += __shfl_xor(h, off, 64);
+    if (live && lane == 0) ent[row] = h;
+  }
+}
+
+// gy [N, A] and gent [N] may each be null (that output took no gradient)
+template <typename T, int G, bool TANH>
+__global__ void __launch_bounds__(256) NO_PACKED_FP32
+    cont_head_bwd_kernel(const T* __restrict__ pre, const float* __restrict__ eps, const T* __restrict__ gy,
+                         const float* __restrict__ gent, T* __restrict__ gpre, long N, int A, float init_std,
+                         float min_std, float max_std, float clip) {
+  const int lane = threadIdx.x & (G - 1);
+  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  const bool live = row < N;
+  if (!live) row = N - 1;
+  float ge = 0.f;
+  if constexpr (!TANH) {
+    // the group's first lane reads the row's entropy gradient for all of it
+    if (gent && lane == 0) ge = gent[row];
+    ge = __shfl(ge, (threadIdx.x & 63) & ~(G - 1), 64);
+  }
+  if (!live) return;
+  const T* pr = pre + row * 2L * A;
+  const float* er = eps + row * (long)A;
+  const T* gr = gy ? gy + row * (long)A : nullptr;
+  T* gp = gpre + row * 2L * A;
+  for (int j = lane; j < A; j += G) {
+    const ContHeadCol c =
+        cont_head_col<T, TANH>(ld(pr, j), ld(pr, A + j), er[j], init_std, min_std, max_std, clip);
+    const float gx = gr ? ld(gr, j) * c.f : 0.f;
+    float gsd = gx * c.dxs;
+    if constexpr (!TANH) gsd += ge / c.sd;
+    st(gp, j, gx * c.dxa);
+    st(gp, A + j, gsd * c.dsb);
+  }
+}
+
+// Group width of a [N, 2A] head: the next power of two >= A within [4, 64];
+// A > 64 keeps 64 (one wave per row, column loop).  N does not enter today.
+int cont_head_group(long N, long A) {
+  (void)N;
+  int G = 4;
+  while (G < A && G < 64) G <<= 1;
+  return G;
+}
+
+// Python-visible query (no device call)
+int cont_head_route(long N, long A) {
+  TORCH_CHECK(N >= 0 && A >= 1, "cont_head_route: N >= 0 and A >= 1");
+  return cont_head_group(N, A);
+}
+
+// Shape checks shared by both directions; returns (N, A, G, blocks).
+std::tuple<long, int, int, int> cont_head_geometry(const torch::Tensor& pre, const torch::Tensor& eps, long mode) {
+  CHECK_IN(pre);
+  CHECK_IN(eps);
+  TORCH_CHECK(mode == 0 || mode == 1, "cont_head: mode is 0 (scaled_normal) or 1 (tanh_normal)");
+  TORCH_CHECK(pre.dim() == 2 && pre.size(1) >= 2 && pre.size(1) % 2 == 0, "cont_head: pre must be [N, 2A]");
+  const long N = pre.size(0);
+  const long A = pre.size(1) / 2;
+  TORCH_CHECK(eps.scalar_type() == at::kFloat && eps.dim() == 2 && eps.size(0) == N && eps.size(1) == A,
+              "cont_head: eps must be fp32 [N, A]");
+  const int G = cont_head_group(N, A);
+  const long blocks = (N * G + kBlock - 1) / kBlock;
+  TORCH_CHECK(A <= INT_MAX / 2 && blocks <= INT_MAX, "cont_head: shape too large for one launch");
+  return {N, (int)A, G, (int)blocks};
+}
+
+// mode 0 returns {actions, entropy[N] fp32}; mode 1 returns {actions}
+std::vector<torch::Tensor> cont_head_fwd(const torch::Tensor& pre, const torch::Tensor& eps, long mode,
+                                         double init_std, double min_std, double max_std, double clip) {
+  const auto [N, A, G, blocks] = cont_head_geometry(pre, eps, mode);
+  auto act = torch::empty({N, (long)A}, pre.options());
+  std::vector<torch::Tensor> out{act};
+  if (mode == 0) out.push_back(torch::empty({N}, pre.options().dtype(at::kFloat)));
+  if (N == 0) return out;
+  float* ent = mode == 0 ? out[1].data_ptr<float>() : nullptr;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long Nn = N;  // structured bindings do not capture into the dispatch lambdas
+  const int An = A, blk = blocks;
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pre.scalar_type(), "cont_head_fwd", [&] {
+    using T = scalar_t;
+    with_bool(mode == 1, [&](auto tanh_mode) {
+      with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
+        hipLaunchKernelGGL((cont_head_fwd_kernel<T, decltype(group)::value, decltype(tanh_mode)::value>),
+                           dim3(blk), dim3(kBlock), 0, stream.stream(), (const T*)pre.data_ptr(),
+                           eps.data_ptr<float>(), (T*)act.data_ptr(), ent, Nn, An, (float)init_std,
+                           (float)min_std, (float)max_std, (float)clip);
+      });
+    });
+  });
+  return out;
+}
+
+torch::Tensor cont_head_bwd(const torch::Tensor& pre, const torch::Tensor& eps,
+                            const c10::optional<torch::Tensor>& g_actions,
+                            const c10::optional<torch::Tensor>& g_entropy, long mode, double init_std,
+                            double min_std, double max_std, double clip) {
+  const auto [N, A, G, blocks] = cont_head_geometry(pre, eps, mode);
+  const bool has_gy = g_actions.has_value() && g_actions->defined();
+  const bool has_ge = mode == 0 && g_entropy.has_value() && g_entropy->defined();
+  if (has_gy) {
+    CHECK_IN((*g_actions));
+    TORCH_CHECK(g_actions->scalar_type() == pre.scalar_type() && g_actions->numel() == N * A,
+                "cont_head_bwd: g_actions must be [N, A] in pre's dtype");
+  }
+  if (has_ge) {
+    CHECK_IN((*g_entropy));
+    TORCH_CHECK(g_entropy->scalar_type() == at::kFloat && g_entropy->numel() == N,
+                "cont_head_bwd: g_entropy must be fp32 [N]");
+  }
+  auto gpre = torch::empty_like(pre);
+  if (N == 0) return gpre;
+  const void* gy = has_gy ? g_actions->data_ptr() : nullptr;
+  const float* ge = has_ge ? g_entropy->data_ptr<float>() : nullptr;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long Nn = N;
+  const int An = A, blk = blocks;
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pre.scalar_type(), "cont_head_bwd", [&] {
+    using T = scalar_t;
+    with_bool(mode == 1, [&](auto tanh_mode) {
+      with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
+        hipLaunchKernelGGL((cont_head_bwd_kernel<T, decltype(group)::value, decltype(tanh_mode)::value>),
+                           dim3(blk), dim3(kBlock), 0, stream.stream(), (const T*)pre.data_ptr(),
+                           eps.data_ptr<float>(), (const T*)gy, ge, (T*)gpre.data_ptr(), Nn, An,
+                           (float)init_std, (float)min_std, (float)max_std, (float)clip);
+      });
+    });
+  });
+  return gpre;
+}
+
+// ---------------------------------------------------------------------------
 // Fused PPO losses (parity: sheeprl/algos/ppo/loss.py
 // — policy_loss :6, value_loss :45, entropy_loss :65).  One reduction kernel
 // computes the clipped policy loss, (optionally clipped) value loss and
@@ -6793,6 +7023,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moments_update", &moments_update);
   m.def("tanh_normal_fwd", &tanh_normal_fwd);
   m.def("tanh_normal_bwd", &tanh_normal_bwd);
+  m.def("cont_head_route", &cont_head_route, py::arg("N"), py::arg("A"));
+  m.def("cont_head_fwd", &cont_head_fwd, py::arg("pre"), py::arg("eps"), py::arg("mode"), py::arg("init_std"),
+        py::arg("min_std"), py::arg("max_std"), py::arg("clip"));
+  m.def("cont_head_bwd", &cont_head_bwd, py::arg("pre"), py::arg("eps"), py::arg("g_actions"),
+        py::arg("g_entropy"), py::arg("mode"), py::arg("init_std"), py::arg("min_std"), py::arg("max_std"),
+        py::arg("clip"));
   m.def("ppo_loss_fwd", &ppo_loss_fwd);
   m.def("ppo_loss_bwd", &ppo_loss_bwd);
   m.def("vloss2_fwd", &vloss2_fwd);

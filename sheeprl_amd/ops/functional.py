@@ -391,6 +391,78 @@ def tanh_normal_sample(mean: Tensor, logstd: Tensor, eps: Tensor, scale: Tensor,
     return _TanhNormalSample.apply(mean, logstd, eps, scale, bias, like, lmin, lmax)
 
 
+_CONT_HEAD_MODES = {"scaled_normal": 0, "tanh_normal": 1}
+
+
+def _cont_head_torch(pre: Tensor, eps: Tensor, mode: str, init_std: float, min_std: float,
+                     max_std: float, clip: float) -> Tuple[Tensor, Optional[Tensor]]:
+    """The head's formulas as a torch composition (CPU tensors and
+    SHEEPRL_AMD_DISABLE_EXT=1); autograd differentiates it."""
+    a, b = torch.chunk(pre.float(), 2, -1)
+    if mode == "tanh_normal":
+        sd = torch.nn.functional.softplus(b + init_std) + min_std
+        x = torch.tanh(5 * torch.tanh(a / 5) + sd * eps)
+        entropy = None
+    else:
+        sd = (max_std - min_std) * torch.sigmoid(b + init_std) + min_std
+        x = torch.tanh(a) + sd * eps
+        entropy = (1.4189385332046727 + torch.log(sd)).sum(-1)
+    if clip > 0.0:
+        x = x * (clip / x.abs().clamp(min=clip)).detach()
+    return x.to(pre.dtype), entropy
+
+
+class _ContinuousActorHead(torch.autograd.Function):
+    """Fused continuous actor head of the Dreamer family: reparameterized
+    sample, action clip and per-row entropy in one kernel each way.  Saves
+    only ``pre`` and ``eps``; the backward recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, pre: Tensor, eps: Tensor, mode: int, init_std: float, min_std: float,
+                max_std: float, clip: float):
+        out = require_ext().cont_head_fwd(pre, eps, mode, init_std, min_std, max_std, clip)
+        ctx.save_for_backward(pre, eps)
+        ctx.meta = (mode, init_std, min_std, max_std, clip)
+        # either output may go unused (the actor loss takes only the entropy)
+        ctx.set_materialize_grads(False)
+        return out[0], (out[1] if mode == 0 else None)
+
+    @staticmethod
+    def backward(ctx, g_actions: Optional[Tensor], g_entropy: Optional[Tensor]):
+        pre, eps = ctx.saved_tensors
+        if g_actions is not None:
+            g_actions = g_actions.to(pre.dtype).contiguous()
+        if g_entropy is not None:
+            g_entropy = g_entropy.float().contiguous()
+        g_pre = require_ext().cont_head_bwd(pre, eps, g_actions, g_entropy, *ctx.meta)
+        return g_pre, None, None, None, None, None, None
+
+
+def continuous_actor_head(pre: Tensor, eps: Tensor, mode: str, init_std: float, min_std: float,
+                          max_std: float, clip: float) -> Tuple[Tensor, Optional[Tensor]]:
+    """Sample, clip and entropy of a continuous Dreamer actor head.
+
+    ``pre`` [..., 2A] is the head layer's output (mean logits, then std
+    logits), ``eps`` [..., A] fp32 standard normal noise, ``mode``
+    ``"scaled_normal"`` or ``"tanh_normal"``.  Returns ``(actions [..., A]`` in
+    ``pre``'s dtype, ``entropy [...]`` fp32 — ``None`` for ``tanh_normal``,
+    whose entropy has no closed form).  ``clip > 0`` rescales actions into
+    ``[-clip, clip]`` with the factor held constant for the gradient."""
+    if mode not in _CONT_HEAD_MODES:
+        raise ValueError(f"continuous_actor_head: unknown mode '{mode}'")
+    lead, A = pre.shape[:-1], pre.shape[-1] // 2
+    if pre.shape[-1] != 2 * A or tuple(eps.shape) != (*lead, A):
+        raise ValueError(f"continuous_actor_head: pre {tuple(pre.shape)} and eps {tuple(eps.shape)} do not match")
+    args = (float(init_std), float(min_std), float(max_std), float(clip))
+    if not use_hip(pre):
+        return _cont_head_torch(pre, eps, mode, *args)
+    actions, entropy = _ContinuousActorHead.apply(
+        pre.reshape(-1, 2 * A).contiguous(), eps.detach().float().reshape(-1, A).contiguous(),
+        _CONT_HEAD_MODES[mode], *args,
+    )
+    return actions.view(*lead, A), (entropy.view(lead) if entropy is not None else None)
+
+
 class _PPOLosses(torch.autograd.Function):
     """Fused PPO clip losses (parity:
     sheeprl/algos/ppo/loss.py:6-65): one reduction kernel returns the
