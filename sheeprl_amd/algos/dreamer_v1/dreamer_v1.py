@@ -65,8 +65,29 @@ def _unit_scale(x):
     scalar with a pageable H2D copy, which is illegal inside hipGraph capture."""
     return torch.ones((), device=x.device, dtype=x.dtype)
 
-def compute_stochastic_state(info: Tensor, min_std: float = 0.1):
-    """(mean, std), sample — parity: dreamer_v1/utils.py:80-108."""
+def fused_gauss_state(x: Tensor) -> bool:
+    """Whether the Normal latent and its KL take ops.gaussian_state /
+    ops.normal_kl (SHEEPRL_AMD_GAUSS_STATE=0 puts the torch chains back)."""
+    return ops.use_hip(x) and os.environ.get("SHEEPRL_AMD_GAUSS_STATE", "1") == "1"
+
+
+def normal_state_kl(post_means: Tensor, post_stds: Tensor, prior_means: Tensor, prior_stds: Tensor) -> Tensor:
+    """Mean over [T, B] of KL(posterior || prior) of the Normal latents."""
+    if fused_gauss_state(post_means):
+        return ops.normal_kl(post_means, post_stds, prior_means, prior_stds).mean()
+    posteriors_dist = td.Independent(td.Normal(post_means, post_stds), 1)
+    priors_dist = td.Independent(td.Normal(prior_means, prior_stds), 1)
+    return td.kl_divergence(posteriors_dist, priors_dist).mean()
+
+
+def compute_stochastic_state(info: Tensor, min_std: float = 0.1, want_stats: bool = True):
+    """(mean, std), sample — parity: dreamer_v1/utils.py:80-108.  On the fused
+    path ``want_stats=False`` returns ``(None, None)`` for the statistics."""
+    if fused_gauss_state(info):
+        # one randn per call, so the draw is safe under graph capture
+        eps = torch.randn(*info.shape[:-1], info.shape[-1] // 2, dtype=torch.float32, device=info.device)
+        sample, mean, std = ops.gaussian_state(info, eps, min_std, want_stats)
+        return (mean, std), sample
     mean, std = torch.chunk(info.float(), 2, -1)
     std = F.softplus(std) + min_std
     dist = td.Independent(td.Normal(mean, std), 1)
@@ -100,9 +121,9 @@ class RSSMV1(nn.Module):
         (mean, std), sample = compute_stochastic_state(info, self.min_std)
         return (mean, std), sample.to(dt)
 
-    def _transition(self, recurrent_state):
+    def _transition(self, recurrent_state, want_stats: bool = True):
         info = self.transition_model(recurrent_state.to(self._dtype))
-        (mean, std), sample = compute_stochastic_state(info, self.min_std)
+        (mean, std), sample = compute_stochastic_state(info, self.min_std, want_stats)
         return (mean, std), sample.to(self._dtype)
 
     def imagination(self, stochastic_state, recurrent_state, actions):
@@ -110,7 +131,7 @@ class RSSMV1(nn.Module):
         recurrent_state = self.recurrent_model(
             torch.cat((stochastic_state.to(dt), actions.to(dt)), -1), recurrent_state.to(dt)
         )
-        _, imagined_state = self._transition(recurrent_state)
+        _, imagined_state = self._transition(recurrent_state, want_stats=False)
         return imagined_state, recurrent_state
 
 
@@ -357,12 +378,9 @@ def train(
 
     pr = _FastUnitNormal(_rm_out, 1)
 
-    posteriors_dist = td.Independent(td.Normal(post_means, post_stds), 1)
-    priors_dist = td.Independent(td.Normal(prior_means, prior_stds), 1)
-
     observation_loss = -sum(po[k].log_prob(batch_obs[k].float()).mean() for k in po)
     reward_loss = -pr.log_prob(data["rewards"]).mean()
-    kl = td.kl_divergence(posteriors_dist, priors_dist).mean()
+    kl = normal_state_kl(post_means, post_stds, prior_means, prior_stds)
     state_loss = torch.clamp(kl, min=cfg.algo.world_model.kl_free_nats)
     continue_loss = torch.zeros((), device=device)
     if cfg.algo.world_model.get("use_continues", False) and world_model.continue_model is not None:

@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 from sheeprl_amd import ops
 from sheeprl_amd.algos.dreamer_v1.dreamer_v1 import build_agent as dv1_build_agent
+from sheeprl_amd.algos.dreamer_v1.dreamer_v1 import normal_state_kl
 from sheeprl_amd.algos.dreamer_v3.agent import Actor, init_weights
 from sheeprl_amd.algos.dreamer_v3.utils import prepare_obs, test
 from sheeprl_amd.config import save_config
@@ -140,11 +141,9 @@ def train(runtime, world_model, ensembles, actor_task, critic_task, actor_explor
     _rm_out = world_model.reward_model(latent_states).float()
 
     pr = _FastUnitNormal(_rm_out, 1)
-    posteriors_dist = td.Independent(td.Normal(post_means, post_stds), 1)
-    priors_dist = td.Independent(td.Normal(prior_means, prior_stds), 1)
     observation_loss = -sum(po[k].log_prob(batch_obs[k].float()).mean() for k in po)
     reward_loss = -pr.log_prob(data["rewards"]).mean()
-    kl = td.kl_divergence(posteriors_dist, priors_dist).mean()
+    kl = normal_state_kl(post_means, post_stds, prior_means, prior_stds)
     state_loss = torch.clamp(kl, min=cfg.algo.world_model.kl_free_nats)
     rec_loss = cfg.algo.world_model.kl_regularizer * state_loss + observation_loss + reward_loss
     world_optimizer.zero_grad(set_to_none=True)

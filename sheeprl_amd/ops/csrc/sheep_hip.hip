@@ -6816,6 +6816,277 @@ torch::Tensor cont_head_bwd(const torch::Tensor& pre, const torch::Tensor& eps,
 }
 
 // ---------------------------------------------------------------------------
+// Diagonal-Normal latent of Dreamer-V1 / Plan2Explore-DV1
+// (dreamer_v1.py compute_stochastic_state) and the KL between two such
+// latents, in the lane-group layout of the actor head above: a row owns an
+// aligned group of G lanes (cont_head_group), lane j keeps column j in
+// registers, S > 64 loops over columns with G = 64.  No LDS, no atomics.
+//   gauss_state: pre = [N, 2S] (columns [0, S) mean a, [S, 2S) raw std b),
+//                sd = softplus(b) + min_std, x = a + sd*eps; mean and sd are
+//                stored in fp32 only where the caller wants them (the
+//                imagination rollout keeps the sample alone).  Backward
+//                saves pre and eps and recomputes:
+//                g_a = g_mean + g_x, g_b = (g_sd + g_x*eps) * sigmoid(b).
+//   normal_kl  : kl[row] = sum_j log(qs/ps) + (ps^2 + (pm-qm)^2)/(2 qs^2) - 1/2
+//                over four fp32 [N, S] inputs, a G-lane butterfly whose idle
+//                lanes hold 0; backward from the closed forms, one store
+//                stream per input that takes a gradient.
+// ---------------------------------------------------------------------------
+
+// overflow-safe softplus, as in cont_head_col
+template <typename T>
+__device__ __forceinline__ float tsoftplus(float z) {
+  if constexpr (sizeof(T) == 2)
+    return fmaxf(z, 0.f) + __logf(1.f + __expf(-fabsf(z)));
+  else
+    return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
+}
+
+// mean [N, S] and sd [N, S] are written only when STATS
+template <typename T, int G, bool STATS>
+__global__ void __launch_bounds__(256) NO_PACKED_FP32
+    gauss_state_fwd_kernel(const T* __restrict__ pre, const float* __restrict__ eps, T* __restrict__ x,
+                           float* __restrict__ mean, float* __restrict__ sd, long N, int S, float min_std) {
+  const int lane = threadIdx.x & (G - 1);
+  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  // groups past the last row recompute it and store nothing
+  const bool live = row < N;
+  if (!live) row = N - 1;
+  const T* pr = pre + row * 2L * S;
+  const long base = row * (long)S;
+  for (int j = lane; j < S; j += G) {
+    const float a = ld(pr, j);
+    const float s = tsoftplus<T>(ld(pr, S + j)) + min_std;
+    const float v = a + s * eps[base + j];
+    if (live) {
+      st(x, base + j, v);
+      if constexpr (STATS) {
+        mean[base + j] = a;
+        sd[base + j] = s;
+      }
+    }
+  }
+}
+
+// gx [N, S] (pre's dtype), gm and gs [N, S] (fp32) may each be null
+template <typename T, int G>
+__global__ void __launch_bounds__(256) NO_PACKED_FP32
+    gauss_state_bwd_kernel(const T* __restrict__ pre, const float* __restrict__ eps, const T* __restrict__ gx,
+                           const float* __restrict__ gm, const float* __restrict__ gs, T* __restrict__ gpre,
+                           long N, int S) {
+  const int lane = threadIdx.x & (G - 1);
+  const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  if (row >= N) return;  // no shuffles below: idle groups leave
+  const T* pr = pre + row * 2L * S;
+  T* gp = gpre + row * 2L * S;
+  const long base = row * (long)S;
+  for (int j = lane; j < S; j += G) {
+    const float g = gx ? ld(gx, base + j) : 0.f;
+    const float ga = (gm ? gm[base + j] : 0.f) + g;
+    const float gsd = (gs ? gs[base + j] : 0.f) + g * eps[base + j];
+    st(gp, j, ga);
+    st(gp, S + j, gsd * tsigmoid<T>(ld(pr, S + j)));
+  }
+}
+
+template <int G>
+__global__ void __launch_bounds__(256) NO_PACKED_FP32
+    normal_kl_fwd_kernel(const float* __restrict__ pm, const float* __restrict__ ps, const float* __restrict__ qm,
+                         const float* __restrict__ qs, float* __restrict__ kl, long N, int S) {
+  const int lane = threadIdx.x & (G - 1);
+  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  // groups past the last row recompute it and store nothing: every lane of
+  // the wave stays in the shuffles
+  const bool live = row < N;
+  if (!live) row = N - 1;
+  const long base = row * (long)S;
+  float h = 0.f;
+  for (int j = lane; j < S; j += G) {
+    const float p = ps[base + j], q = qs[base + j], d = pm[base + j] - qm[base + j];
+    const float iq = 1.f / q;
+    h += logf(q / p) + 0.5f * (p * p + d * d) * iq * iq - 0.5f;
+  }
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) h += __shfl_xor(h, off, 64);
+  if (live && lane == 0) kl[row] = h;
+}
+
+// gpm, gps, gqm, gqs [N, S] may each be null (that input takes no gradient)
+template <int G>
+__global__ void __launch_bounds__(256) NO_PACKED_FP32
+    normal_kl_bwd_kernel(const float* __restrict__ pm, const float* __restrict__ ps, const float* __restrict__ qm,
+                         const float* __restrict__ qs, const float* __restrict__ gkl, float* __restrict__ gpm,
+                         float* __restrict__ gps, float* __restrict__ gqm, float* __restrict__ gqs, long N,
+                         int S) {
+  const int lane = threadIdx.x & (G - 1);
+  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  const bool live = row < N;
+  if (!live) row = N - 1;
+  // the group's first lane reads the row's gradient for all of it
+  float g = 0.f;
+  if (lane == 0) g = gkl[row];
+  g = __shfl(g, (threadIdx.x & 63) & ~(G - 1), 64);
+  if (!live) return;
+  const long base = row * (long)S;
+  for (int j = lane; j < S; j += G) {
+    const float p = ps[base + j], q = qs[base + j], d = pm[base + j] - qm[base + j];
+    const float iq = 1.f / q;
+    const float iq2 = iq * iq;
+    const float dm = g * d * iq2;
+    if (gpm) gpm[base + j] = dm;
+    if (gqm) gqm[base + j] = -dm;
+    if (gps) gps[base + j] = g * (p * iq2 - 1.f / p);
+    if (gqs) gqs[base + j] = g * (iq - (p * p + d * d) * iq2 * iq);
+  }
+}
+
+// Shape checks shared by both directions; returns (N, S, G, blocks).
+std::tuple<long, int, int, int> gauss_state_geometry(const torch::Tensor& pre, const torch::Tensor& eps) {
+  CHECK_IN(pre);
+  CHECK_IN(eps);
+  TORCH_CHECK(pre.dim() == 2 && pre.size(1) >= 2 && pre.size(1) % 2 == 0, "gauss_state: pre must be [N, 2S]");
+  TORCH_CHECK(pre.scalar_type() == at::kFloat || pre.scalar_type() == at::kBFloat16 ||
+                  pre.scalar_type() == at::kHalf,
+              "gauss_state: pre must be fp32, bf16 or half");
+  const long N = pre.size(0);
+  const long S = pre.size(1) / 2;
+  TORCH_CHECK(eps.scalar_type() == at::kFloat && eps.dim() == 2 && eps.size(0) == N && eps.size(1) == S,
+              "gauss_state: eps must be fp32 [N, S]");
+  TORCH_CHECK(eps.device() == pre.device(), "gauss_state: pre and eps must be on one device");
+  const int G = cont_head_group(N, S);
+  const long blocks = (N * G + kBlock - 1) / kBlock;
+  TORCH_CHECK(S <= INT_MAX / 2 && blocks <= INT_MAX, "gauss_state: shape too large for one launch");
+  return {N, (int)S, G, (int)blocks};
+}
+
+// returns {sample} or, with want_stats, {sample, mean fp32, std fp32}
+std::vector<torch::Tensor> gauss_state_fwd(const torch::Tensor& pre, const torch::Tensor& eps, double min_std,
+                                           bool want_stats) {
+  const auto [N, S, G, blocks] = gauss_state_geometry(pre, eps);
+  std::vector<torch::Tensor> out{torch::empty({N, (long)S}, pre.options())};
+  if (want_stats) {
+    out.push_back(torch::empty({N, (long)S}, pre.options().dtype(at::kFloat)));
+    out.push_back(torch::empty({N, (long)S}, pre.options().dtype(at::kFloat)));
+  }
+  if (N == 0) return out;
+  float* mean = want_stats ? out[1].data_ptr<float>() : nullptr;
+  float* sd = want_stats ? out[2].data_ptr<float>() : nullptr;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long Nn = N;  // structured bindings do not capture into the dispatch lambdas
+  const int Sn = S, blk = blocks;
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pre.scalar_type(), "gauss_state_fwd", [&] {
+    using T = scalar_t;
+    with_bool(want_stats, [&](auto stats) {
+      with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
+        hipLaunchKernelGGL((gauss_state_fwd_kernel<T, decltype(group)::value, decltype(stats)::value>),
+                           dim3(blk), dim3(kBlock), 0, stream.stream(), (const T*)pre.data_ptr(),
+                           eps.data_ptr<float>(), (T*)out[0].data_ptr(), mean, sd, Nn, Sn, (float)min_std);
+      });
+    });
+  });
+  return out;
+}
+
+torch::Tensor gauss_state_bwd(const torch::Tensor& pre, const torch::Tensor& eps,
+                              const c10::optional<torch::Tensor>& g_sample,
+                              const c10::optional<torch::Tensor>& g_mean,
+                              const c10::optional<torch::Tensor>& g_std) {
+  const auto [N, S, G, blocks] = gauss_state_geometry(pre, eps);
+  const long numel = N * S;
+  // an absent gradient is a null pointer in the kernel
+  auto grad_ptr = [&](const c10::optional<torch::Tensor>& g, at::ScalarType dtype, const char* what) {
+    if (!g.has_value() || !g->defined()) return (const void*)nullptr;
+    TORCH_CHECK(g->is_cuda() && g->is_contiguous() && g->device() == pre.device() &&
+                    g->scalar_type() == dtype && g->numel() == numel,
+                "gauss_state_bwd: ", what);
+    return (const void*)g->data_ptr();
+  };
+  const void* gx = grad_ptr(g_sample, pre.scalar_type(), "g_sample must be contiguous [N, S] in pre's dtype");
+  const void* gm = grad_ptr(g_mean, at::kFloat, "g_mean must be contiguous fp32 [N, S]");
+  const void* gs = grad_ptr(g_std, at::kFloat, "g_std must be contiguous fp32 [N, S]");
+  auto gpre = torch::empty_like(pre);
+  if (N == 0) return gpre;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long Nn = N;
+  const int Sn = S, blk = blocks;
+  AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pre.scalar_type(), "gauss_state_bwd", [&] {
+    using T = scalar_t;
+    with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
+      hipLaunchKernelGGL((gauss_state_bwd_kernel<T, decltype(group)::value>), dim3(blk), dim3(kBlock), 0,
+                         stream.stream(), (const T*)pre.data_ptr(), eps.data_ptr<float>(), (const T*)gx,
+                         (const float*)gm, (const float*)gs, (T*)gpre.data_ptr(), Nn, Sn);
+    });
+  });
+  return gpre;
+}
+
+// Shape checks shared by both directions; returns (N, S, G, blocks).
+std::tuple<long, int, int, int> normal_kl_geometry(const torch::Tensor& pm, const torch::Tensor& ps,
+                                                   const torch::Tensor& qm, const torch::Tensor& qs) {
+  CHECK_IN(pm);
+  CHECK_IN(ps);
+  CHECK_IN(qm);
+  CHECK_IN(qs);
+  TORCH_CHECK(pm.dim() == 2 && pm.size(1) >= 1, "normal_kl: inputs must be [N, S]");
+  for (const torch::Tensor* t : {&pm, &ps, &qm, &qs})
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->sizes() == pm.sizes() && t->device() == pm.device(),
+                "normal_kl: pm, ps, qm, qs must be fp32 tensors of one shape on one device");
+  const long N = pm.size(0);
+  const long S = pm.size(1);
+  const int G = cont_head_group(N, S);
+  const long blocks = (N * G + kBlock - 1) / kBlock;
+  TORCH_CHECK(S <= INT_MAX && blocks <= INT_MAX, "normal_kl: shape too large for one launch");
+  return {N, (int)S, G, (int)blocks};
+}
+
+// per-row KL(N(pm, ps) || N(qm, qs)) summed over the columns, fp32 [N]
+torch::Tensor normal_kl_fwd(const torch::Tensor& pm, const torch::Tensor& ps, const torch::Tensor& qm,
+                            const torch::Tensor& qs) {
+  const auto [N, S, G, blocks] = normal_kl_geometry(pm, ps, qm, qs);
+  auto kl = torch::empty({N}, pm.options());
+  if (N == 0) return kl;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long Nn = N;
+  const int Sn = S, blk = blocks;
+  with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
+    hipLaunchKernelGGL((normal_kl_fwd_kernel<decltype(group)::value>), dim3(blk), dim3(kBlock), 0,
+                       stream.stream(), pm.data_ptr<float>(), ps.data_ptr<float>(), qm.data_ptr<float>(),
+                       qs.data_ptr<float>(), kl.data_ptr<float>(), Nn, Sn);
+  });
+  return kl;
+}
+
+// returns {g_pm, g_ps, g_qm, g_qs}; an input whose need flag is false gets an
+// undefined tensor (None in Python) and no stores
+std::vector<torch::Tensor> normal_kl_bwd(const torch::Tensor& pm, const torch::Tensor& ps,
+                                         const torch::Tensor& qm, const torch::Tensor& qs,
+                                         const torch::Tensor& g_kl, bool need_pm, bool need_ps, bool need_qm,
+                                         bool need_qs) {
+  const auto [N, S, G, blocks] = normal_kl_geometry(pm, ps, qm, qs);
+  CHECK_IN(g_kl);
+  TORCH_CHECK(g_kl.scalar_type() == at::kFloat && g_kl.numel() == N && g_kl.device() == pm.device(),
+              "normal_kl_bwd: g_kl must be fp32 [N]");
+  const bool need[4] = {need_pm, need_ps, need_qm, need_qs};
+  std::vector<torch::Tensor> out(4);
+  float* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 4; ++i) {
+    if (!need[i]) continue;
+    out[i] = torch::empty_like(pm);
+    ptr[i] = N > 0 ? out[i].data_ptr<float>() : nullptr;
+  }
+  if (N == 0) return out;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long Nn = N;
+  const int Sn = S, blk = blocks;
+  with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
+    hipLaunchKernelGGL((normal_kl_bwd_kernel<decltype(group)::value>), dim3(blk), dim3(kBlock), 0,
+                       stream.stream(), pm.data_ptr<float>(), ps.data_ptr<float>(), qm.data_ptr<float>(),
+                       qs.data_ptr<float>(), g_kl.data_ptr<float>(), ptr[0], ptr[1], ptr[2], ptr[3], Nn, Sn);
+  });
+  return out;
+}
+
+// ---------------------------------------------------------------------------
 // Fused PPO losses (parity: sheeprl/algos/ppo/loss.py
 // — policy_loss :6, value_loss :45, entropy_loss :65).  One reduction kernel
 // computes the clipped policy loss, (optionally clipped) value loss and
@@ -7029,6 +7300,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cont_head_bwd", &cont_head_bwd, py::arg("pre"), py::arg("eps"), py::arg("g_actions"),
         py::arg("g_entropy"), py::arg("mode"), py::arg("init_std"), py::arg("min_std"), py::arg("max_std"),
         py::arg("clip"));
+  m.def("gauss_state_fwd", &gauss_state_fwd, py::arg("pre"), py::arg("eps"), py::arg("min_std"),
+        py::arg("want_stats"));
+  m.def("gauss_state_bwd", &gauss_state_bwd, py::arg("pre"), py::arg("eps"), py::arg("g_sample"),
+        py::arg("g_mean"), py::arg("g_std"));
+  m.def("normal_kl_fwd", &normal_kl_fwd, py::arg("pm"), py::arg("ps"), py::arg("qm"), py::arg("qs"));
+  m.def("normal_kl_bwd", &normal_kl_bwd, py::arg("pm"), py::arg("ps"), py::arg("qm"), py::arg("qs"),
+        py::arg("g_kl"), py::arg("need_pm"), py::arg("need_ps"), py::arg("need_qm"), py::arg("need_qs"));
   m.def("ppo_loss_fwd", &ppo_loss_fwd);
   m.def("ppo_loss_bwd", &ppo_loss_bwd);
   m.def("vloss2_fwd", &vloss2_fwd);

@@ -463,6 +463,99 @@ def continuous_actor_head(pre: Tensor, eps: Tensor, mode: str, init_std: float, 
     return actions.view(*lead, A), (entropy.view(lead) if entropy is not None else None)
 
 
+def _gauss_state_torch(pre: Tensor, eps: Tensor, min_std: float,
+                       want_stats: bool) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+    """The latent's formulas as a torch composition (CPU tensors and
+    SHEEPRL_AMD_DISABLE_EXT=1); autograd differentiates it."""
+    mean, b = torch.chunk(pre.float(), 2, -1)
+    std = torch.nn.functional.softplus(b) + min_std
+    sample = (mean + std * eps).to(pre.dtype)
+    return (sample, mean, std) if want_stats else (sample, None, None)
+
+
+class _GaussianState(torch.autograd.Function):
+    """Fused diagonal-Normal latent of Dreamer-V1: softplus std and the
+    reparameterized sample in one kernel each way.  Saves only ``pre`` and
+    ``eps``; the backward recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, pre: Tensor, eps: Tensor, min_std: float, want_stats: bool):
+        out = require_ext().gauss_state_fwd(pre, eps, min_std, want_stats)
+        ctx.save_for_backward(pre, eps)
+        # any output may go unused (the KL takes the stats, the rollout the sample)
+        ctx.set_materialize_grads(False)
+        return (out[0], out[1], out[2]) if want_stats else (out[0], None, None)
+
+    @staticmethod
+    def backward(ctx, g_sample: Optional[Tensor], g_mean: Optional[Tensor], g_std: Optional[Tensor]):
+        pre, eps = ctx.saved_tensors
+        if g_sample is not None:
+            g_sample = g_sample.to(pre.dtype).contiguous()
+        if g_mean is not None:
+            g_mean = g_mean.float().contiguous()
+        if g_std is not None:
+            g_std = g_std.float().contiguous()
+        return require_ext().gauss_state_bwd(pre, eps, g_sample, g_mean, g_std), None, None, None
+
+
+def gaussian_state(pre: Tensor, eps: Tensor, min_std: float,
+                   want_stats: bool = True) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor]]:
+    """Reparameterized sample of a diagonal-Normal latent state.
+
+    ``pre`` [..., 2S] is the state model's output (means, then raw stds),
+    ``eps`` [..., S] fp32 standard normal noise.  With ``std = softplus(raw) +
+    min_std`` returns ``(sample [..., S]`` in ``pre``'s dtype, ``mean``,
+    ``std)``, the last two fp32 [..., S], or ``None`` without ``want_stats``."""
+    lead, S = pre.shape[:-1], pre.shape[-1] // 2
+    if pre.shape[-1] != 2 * S or S == 0 or tuple(eps.shape) != (*lead, S):
+        raise ValueError(f"gaussian_state: pre {tuple(pre.shape)} and eps {tuple(eps.shape)} do not match")
+    if not use_hip(pre):
+        return _gauss_state_torch(pre, eps, float(min_std), want_stats)
+    sample, mean, std = _GaussianState.apply(
+        pre.reshape(-1, 2 * S).contiguous(), eps.detach().float().reshape(-1, S).contiguous(),
+        float(min_std), bool(want_stats),
+    )
+    if not want_stats:
+        return sample.view(*lead, S), None, None
+    return sample.view(*lead, S), mean.view(*lead, S), std.view(*lead, S)
+
+
+def _normal_kl_torch(pm: Tensor, ps: Tensor, qm: Tensor, qs: Tensor) -> Tensor:
+    """KL(N(pm, ps) || N(qm, qs)) summed over the last dimension, as a torch
+    composition (CPU tensors and SHEEPRL_AMD_DISABLE_EXT=1)."""
+    pm, ps, qm, qs = pm.float(), ps.float(), qm.float(), qs.float()
+    return (torch.log(qs / ps) + (ps.square() + (pm - qm).square()) / (2 * qs.square()) - 0.5).sum(-1)
+
+
+class _NormalKL(torch.autograd.Function):
+    """Per-row KL between two diagonal Normals, one kernel each way; the
+    backward writes only the gradients of inputs that require one."""
+
+    @staticmethod
+    def forward(ctx, pm: Tensor, ps: Tensor, qm: Tensor, qs: Tensor) -> Tensor:
+        ctx.save_for_backward(pm, ps, qm, qs)
+        return require_ext().normal_kl_fwd(pm, ps, qm, qs)
+
+    @staticmethod
+    def backward(ctx, g_kl: Tensor):
+        grads = require_ext().normal_kl_bwd(
+            *ctx.saved_tensors, g_kl.float().contiguous(), *ctx.needs_input_grad[:4]
+        )
+        return tuple(grads)
+
+
+def normal_kl(pm: Tensor, ps: Tensor, qm: Tensor, qs: Tensor) -> Tensor:
+    """KL(N(pm, ps) || N(qm, qs)) of diagonal Normals [..., S], summed over the
+    last dimension: fp32 [...].  ``pm``/``ps`` are the posterior's mean and
+    std, ``qm``/``qs`` the prior's."""
+    lead, S = pm.shape[:-1], pm.shape[-1]
+    if S == 0 or any(t.shape != pm.shape for t in (ps, qm, qs)):
+        raise ValueError(f"normal_kl: shapes {[tuple(t.shape) for t in (pm, ps, qm, qs)]} do not match")
+    if not use_hip(pm):
+        return _normal_kl_torch(pm, ps, qm, qs)
+    return _NormalKL.apply(*(t.float().reshape(-1, S).contiguous() for t in (pm, ps, qm, qs))).view(lead)
+
+
 class _PPOLosses(torch.autograd.Function):
     """Fused PPO clip losses (parity:
     sheeprl/algos/ppo/loss.py:6-65): one reduction kernel returns the
