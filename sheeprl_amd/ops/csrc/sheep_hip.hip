@@ -144,6 +144,78 @@ __device__ __forceinline__ void st<__hip_bfloat16>(__hip_bfloat16* p, long i, fl
 }
 
 // ---------------------------------------------------------------------------
+// Lane-group layout, for many rows of very short rows: a row owns an aligned
+// group of G lanes (G = lane_group_width(cols): the next power of two >= cols
+// within [4, 64]), so 64/G rows share a wave and a block covers 4*64/G rows.
+// Lane j keeps column j in registers; cols > 64 is G = 64, one wave per row,
+// with the column loop `for (j = lane; j < cols; j += G)` taken more than
+// once.  No LDS, no atomics.
+// The idle-group rule: a group past the last row is clamped to row N-1,
+// recomputes it and stores nothing, so every lane of the wave stays in the
+// shuffles.  Kernels test `live` before each store.
+// ---------------------------------------------------------------------------
+
+// Most lane-group kernels are built without packed-fp32 instructions (libm's
+// tanhf/log1pf expansions otherwise pair their polynomial steps into them).
+// group_sum and group_first carry the attribute as their callers do, so the
+// runtime's __shfl/__shfl_xor stay the calls they have been in those kernels.
+#define NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
+
+template <int G>
+__device__ __forceinline__ int group_lane() {
+  return threadIdx.x & (G - 1);
+}
+template <int G>
+__device__ __forceinline__ long group_row(long N, bool& live) {
+  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  live = row < N;
+  if (!live) row = N - 1;
+  return row;
+}
+// sum over the group's lanes; lanes without a column pass 0
+template <int G>
+__device__ __forceinline__ NO_PACKED_FP32 float group_sum(float v) {
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+// the value of the group's first lane, in every lane of the group
+template <int G>
+__device__ __forceinline__ NO_PACKED_FP32 float group_first(float v) {
+  return __shfl(v, (threadIdx.x & 63) & ~(G - 1), 64);
+}
+
+int lane_group_width(long cols) {
+  int G = 4;
+  while (G < cols && G < 64) G <<= 1;
+  return G;
+}
+
+// Launch shape of a lane-group kernel over [N, cols]; a plain struct, so the
+// dispatch lambdas capture it.  row_elems is the widest row any operand has
+// (the kernels index columns with int).
+struct LaneGroupGeometry {
+  long N;
+  int cols, G, blocks;
+};
+LaneGroupGeometry lane_group_geometry(const char* op, long N, long cols, long row_elems) {
+  const int G = lane_group_width(cols);
+  const long blocks = (N * G + kBlock - 1) / kBlock;
+  TORCH_CHECK(row_elems <= INT_MAX && blocks <= INT_MAX, op, ": shape too large for one launch");
+  return {N, (int)cols, G, (int)blocks};
+}
+
+// Launches kernel_of(std::integral_constant<int, G>{}), the kernel's
+// instantiation for the geometry's group width, on the current stream.
+template <typename K, typename... Args>
+void lane_group_launch(const LaneGroupGeometry& geo, K&& kernel_of, Args... args) {
+  auto stream = at::cuda::getCurrentCUDAStream();
+  with_int<4, 8, 16, 32, 64>(geo.G, [&](auto group) {
+    hipLaunchKernelGGL(kernel_of(group), dim3(geo.blocks), dim3(kBlock), 0, stream.stream(), args...);
+  });
+}
+
+// ---------------------------------------------------------------------------
 // unimix categorical straight-through cores: the one home of the head's math
 // (mix formula, clamps, sentinels, tie-break, closed-form backward), one core
 // per execution shape.  Every cat_st / g16 / pk / scan2 / scan3 sampler
@@ -2347,20 +2419,17 @@ void cat_st_fwd_o(const torch::Tensor& raw, const torch::Tensor& urand, double u
 }
 
 // Inference-only sampler (the no-grad imagination rollout): the one-hots of
-// cat_st_fwd_o without its fp32 m/s outputs.  A row takes an aligned group of
-// G lanes (G = next power of two >= K, at most 64), so 64/G rows share a
-// wave; the math is cat_st_wave_fwd's, hence the same one-hots bit for bit.
+// cat_st_fwd_o without its fp32 m/s outputs, in the lane-group layout
+// (group_row); the math is cat_st_wave_fwd's, hence the same one-hots bit
+// for bit.
 template <typename T, int G>
 __global__ void __launch_bounds__(256)
     cat_st_sample_kernel(const T* __restrict__ raw, const float* __restrict__ urand, T* __restrict__ onehot,
                          long nrows, int K, float unimix, long ohs, long spb, T* __restrict__ onehot2,
                          long oh2s) {
-  const int lane = threadIdx.x & (G - 1);
-  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  // groups past the last row recompute it and store nothing: every lane of
-  // the wave stays in the shuffles
-  const bool live = row < nrows;
-  if (!live) row = nrows - 1;
+  const int lane = group_lane<G>();
+  bool live;
+  const long row = group_row<G>(nrows, live);
   const T* L = raw + row * (long)K;
   const int best_j =
       cat_st_wave_fwd<T, true, G, false>(L, urand + row * (long)K, nullptr, nullptr, K, unimix, lane);
@@ -2403,17 +2472,13 @@ void cat_st_sample_o(const torch::Tensor& raw, const torch::Tensor& urand, doubl
     oh2 = onehot2->data_ptr();
     oh2s = onehot2->stride(0);
   }
-  int G = 4;
-  while (G < K && G < 64) G <<= 1;
-  const int blocks = (int)((nrows * G + kBlock - 1) / kBlock);
-  auto stream = at::cuda::getCurrentCUDAStream();
+  const auto geo = lane_group_geometry("cat_st_sample_o", nrows, K, K);
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, raw.scalar_type(), "cat_st_sample_o", [&] {
     using T = scalar_t;
-    with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
-      hipLaunchKernelGGL((cat_st_sample_kernel<T, decltype(group)::value>), dim3(blocks), dim3(kBlock), 0,
-                         stream.stream(), (const T*)raw.data_ptr(), urand.data_ptr<float>(),
-                         (T*)onehot.data_ptr(), nrows, K, (float)unimix, ohs, spb, (T*)oh2, oh2s);
-    });
+    lane_group_launch(
+        geo, [](auto group) { return cat_st_sample_kernel<T, decltype(group)::value>; },
+        (const T*)raw.data_ptr(), urand.data_ptr<float>(), (T*)onehot.data_ptr(), nrows, K, (float)unimix, ohs,
+        spb, (T*)oh2, oh2s);
   });
 }
 
@@ -6597,22 +6662,23 @@ std::vector<torch::Tensor> tanh_normal_bwd(const torch::Tensor& gaction, const t
 //   tanh_normal  : mu = 5*tanh(a/5), sd = softplus(b+init_std)+min_std,
 //                  x = tanh(mu + sd*eps), no entropy
 //   clip > 0     : y = x*f, f = clip/max(clip, |x|) a constant for the gradient
-// Many rows, very short rows: a row owns an aligned group of G lanes (G = next
-// power of two >= A, 4..64), so 64/G rows share a wave and a block covers
-// 4*64/G rows.  Lane j loads a_j and b_j of its row (two coalesced streams A
-// apart), keeps both columns' math in registers and stores y_j; the entropy is
-// a G-lane butterfly whose idle lanes hold 0.  A > 64 is the G = 64 kernel,
-// one wave per row, with the column loop taken more than once.  Backward
-// saves nothing but pre and eps and recomputes the rest.
+// Lane-group layout (group_row) over the A columns: lane j loads a_j and b_j
+// of its row (two coalesced streams A apart), keeps both columns' math in
+// registers and stores y_j; the entropy is the group's sum.  Backward saves
+// nothing but pre and eps and recomputes the rest.
 // ---------------------------------------------------------------------------
-
-// The two kernels below are built without packed-fp32 instructions (libm's
-// tanhf/log1pf expansions otherwise pair their polynomial steps into them).
-#define NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
 
 template <typename T>
 __device__ __forceinline__ float tsigmoid(float z) {
   return 1.f / (1.f + texp<T>(-z));
+}
+// overflow-safe softplus: max(z, 0) + log(1 + exp(-|z|))
+template <typename T>
+__device__ __forceinline__ float tsoftplus(float z) {
+  if constexpr (sizeof(T) == 2)
+    return fmaxf(z, 0.f) + __logf(1.f + __expf(-fabsf(z)));
+  else
+    return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
 }
 
 // One column of the head: everything the forward stores and the backward
@@ -6632,13 +6698,7 @@ __device__ __forceinline__ ContHeadCol cont_head_col(float a, float b, float e, 
   const float z = b + init_std;
   if constexpr (TANH) {
     const float t = ttanh<T>(a * 0.2f);
-    // overflow-safe softplus: max(z, 0) + log(1 + exp(-|z|))
-    float sp;
-    if constexpr (sizeof(T) == 2)
-      sp = fmaxf(z, 0.f) + __logf(1.f + __expf(-fabsf(z)));
-    else
-      sp = fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
-    c.sd = sp + min_std;
+    c.sd = tsoftplus<T>(z) + min_std;
     c.x = ttanh<T>(5.f * t + c.sd * e);
     const float du = 1.f - c.x * c.x;
     c.dxa = du * (1.f - t * t);
@@ -6662,12 +6722,9 @@ __global__ void __launch_bounds__(256) NO_PACKED_FP32
     cont_head_fwd_kernel(const T* __restrict__ pre, const float* __restrict__ eps, T* __restrict__ act,
                          float* __restrict__ ent, long N, int A, float init_std, float min_std, float max_std,
                          float clip) {
-  const int lane = threadIdx.x & (G - 1);
-  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  // groups past the last row recompute it and store nothing: every lane of
-  // the wave stays in the shuffles
-  const bool live = row < N;
-  if (!live) row = N - 1;
+  const int lane = group_lane<G>();
+  bool live;
+  const long row = group_row<G>(N, live);
   const T* pr = pre + row * 2L * A;
   const float* er = eps + row * (long)A;
   T* yr = act + row * (long)A;
@@ -6682,8 +6739,7 @@ __global__ void __launch_bounds__(256) NO_PACKED_FP32
     if constexpr (!TANH) h += 1.4189385332046727f + tlog<T>(c.sd);  // 0.5 + 0.5*log(2pi)
   }
   if constexpr (!TANH) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) h += __shfl_xor(h, off, 64);
+    h = group_sum<G>(h);
     if (live && lane == 0) ent[row] = h;
   }
 }
@@ -6694,15 +6750,14 @@ __global__ void __launch_bounds__(256) NO_PACKED_FP32
     cont_head_bwd_kernel(const T* __restrict__ pre, const float* __restrict__ eps, const T* __restrict__ gy,
                          const float* __restrict__ gent, T* __restrict__ gpre, long N, int A, float init_std,
                          float min_std, float max_std, float clip) {
-  const int lane = threadIdx.x & (G - 1);
-  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  const bool live = row < N;
-  if (!live) row = N - 1;
+  const int lane = group_lane<G>();
+  bool live;
+  const long row = group_row<G>(N, live);
   float ge = 0.f;
   if constexpr (!TANH) {
     // the group's first lane reads the row's entropy gradient for all of it
     if (gent && lane == 0) ge = gent[row];
-    ge = __shfl(ge, (threadIdx.x & 63) & ~(G - 1), 64);
+    ge = group_first<G>(ge);
   }
   if (!live) return;
   const T* pr = pre + row * 2L * A;
@@ -6720,23 +6775,14 @@ __global__ void __launch_bounds__(256) NO_PACKED_FP32
   }
 }
 
-// Group width of a [N, 2A] head: the next power of two >= A within [4, 64];
-// A > 64 keeps 64 (one wave per row, column loop).  N does not enter today.
-int cont_head_group(long N, long A) {
-  (void)N;
-  int G = 4;
-  while (G < A && G < 64) G <<= 1;
-  return G;
-}
-
-// Python-visible query (no device call)
+// Python-visible query (no device call): the group width of an [N, 2A] head
 int cont_head_route(long N, long A) {
   TORCH_CHECK(N >= 0 && A >= 1, "cont_head_route: N >= 0 and A >= 1");
-  return cont_head_group(N, A);
+  return lane_group_width(A);
 }
 
-// Shape checks shared by both directions; returns (N, A, G, blocks).
-std::tuple<long, int, int, int> cont_head_geometry(const torch::Tensor& pre, const torch::Tensor& eps, long mode) {
+// Shape checks shared by both directions; cols = A.
+LaneGroupGeometry cont_head_geometry(const torch::Tensor& pre, const torch::Tensor& eps, long mode) {
   CHECK_IN(pre);
   CHECK_IN(eps);
   TORCH_CHECK(mode == 0 || mode == 1, "cont_head: mode is 0 (scaled_normal) or 1 (tanh_normal)");
@@ -6745,33 +6791,26 @@ std::tuple<long, int, int, int> cont_head_geometry(const torch::Tensor& pre, con
   const long A = pre.size(1) / 2;
   TORCH_CHECK(eps.scalar_type() == at::kFloat && eps.dim() == 2 && eps.size(0) == N && eps.size(1) == A,
               "cont_head: eps must be fp32 [N, A]");
-  const int G = cont_head_group(N, A);
-  const long blocks = (N * G + kBlock - 1) / kBlock;
-  TORCH_CHECK(A <= INT_MAX / 2 && blocks <= INT_MAX, "cont_head: shape too large for one launch");
-  return {N, (int)A, G, (int)blocks};
+  return lane_group_geometry("cont_head", N, A, 2 * A);
 }
 
 // mode 0 returns {actions, entropy[N] fp32}; mode 1 returns {actions}
 std::vector<torch::Tensor> cont_head_fwd(const torch::Tensor& pre, const torch::Tensor& eps, long mode,
                                          double init_std, double min_std, double max_std, double clip) {
-  const auto [N, A, G, blocks] = cont_head_geometry(pre, eps, mode);
-  auto act = torch::empty({N, (long)A}, pre.options());
+  const auto geo = cont_head_geometry(pre, eps, mode);
+  auto act = torch::empty({geo.N, (long)geo.cols}, pre.options());
   std::vector<torch::Tensor> out{act};
-  if (mode == 0) out.push_back(torch::empty({N}, pre.options().dtype(at::kFloat)));
-  if (N == 0) return out;
+  if (mode == 0) out.push_back(torch::empty({geo.N}, pre.options().dtype(at::kFloat)));
+  if (geo.N == 0) return out;
   float* ent = mode == 0 ? out[1].data_ptr<float>() : nullptr;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const long Nn = N;  // structured bindings do not capture into the dispatch lambdas
-  const int An = A, blk = blocks;
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pre.scalar_type(), "cont_head_fwd", [&] {
     using T = scalar_t;
     with_bool(mode == 1, [&](auto tanh_mode) {
-      with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
-        hipLaunchKernelGGL((cont_head_fwd_kernel<T, decltype(group)::value, decltype(tanh_mode)::value>),
-                           dim3(blk), dim3(kBlock), 0, stream.stream(), (const T*)pre.data_ptr(),
-                           eps.data_ptr<float>(), (T*)act.data_ptr(), ent, Nn, An, (float)init_std,
-                           (float)min_std, (float)max_std, (float)clip);
-      });
+      lane_group_launch(
+          geo,
+          [](auto group) { return cont_head_fwd_kernel<T, decltype(group)::value, decltype(tanh_mode)::value>; },
+          (const T*)pre.data_ptr(), eps.data_ptr<float>(), (T*)act.data_ptr(), ent, geo.N, geo.cols,
+          (float)init_std, (float)min_std, (float)max_std, (float)clip);
     });
   });
   return out;
@@ -6781,35 +6820,31 @@ torch::Tensor cont_head_bwd(const torch::Tensor& pre, const torch::Tensor& eps,
                             const c10::optional<torch::Tensor>& g_actions,
                             const c10::optional<torch::Tensor>& g_entropy, long mode, double init_std,
                             double min_std, double max_std, double clip) {
-  const auto [N, A, G, blocks] = cont_head_geometry(pre, eps, mode);
+  const auto geo = cont_head_geometry(pre, eps, mode);
   const bool has_gy = g_actions.has_value() && g_actions->defined();
   const bool has_ge = mode == 0 && g_entropy.has_value() && g_entropy->defined();
   if (has_gy) {
     CHECK_IN((*g_actions));
-    TORCH_CHECK(g_actions->scalar_type() == pre.scalar_type() && g_actions->numel() == N * A,
+    TORCH_CHECK(g_actions->scalar_type() == pre.scalar_type() && g_actions->numel() == geo.N * geo.cols,
                 "cont_head_bwd: g_actions must be [N, A] in pre's dtype");
   }
   if (has_ge) {
     CHECK_IN((*g_entropy));
-    TORCH_CHECK(g_entropy->scalar_type() == at::kFloat && g_entropy->numel() == N,
+    TORCH_CHECK(g_entropy->scalar_type() == at::kFloat && g_entropy->numel() == geo.N,
                 "cont_head_bwd: g_entropy must be fp32 [N]");
   }
   auto gpre = torch::empty_like(pre);
-  if (N == 0) return gpre;
+  if (geo.N == 0) return gpre;
   const void* gy = has_gy ? g_actions->data_ptr() : nullptr;
   const float* ge = has_ge ? g_entropy->data_ptr<float>() : nullptr;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const long Nn = N;
-  const int An = A, blk = blocks;
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pre.scalar_type(), "cont_head_bwd", [&] {
     using T = scalar_t;
     with_bool(mode == 1, [&](auto tanh_mode) {
-      with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
-        hipLaunchKernelGGL((cont_head_bwd_kernel<T, decltype(group)::value, decltype(tanh_mode)::value>),
-                           dim3(blk), dim3(kBlock), 0, stream.stream(), (const T*)pre.data_ptr(),
-                           eps.data_ptr<float>(), (const T*)gy, ge, (T*)gpre.data_ptr(), Nn, An,
-                           (float)init_std, (float)min_std, (float)max_std, (float)clip);
-      });
+      lane_group_launch(
+          geo,
+          [](auto group) { return cont_head_bwd_kernel<T, decltype(group)::value, decltype(tanh_mode)::value>; },
+          (const T*)pre.data_ptr(), eps.data_ptr<float>(), (const T*)gy, ge, (T*)gpre.data_ptr(), geo.N,
+          geo.cols, (float)init_std, (float)min_std, (float)max_std, (float)clip);
     });
   });
   return gpre;
@@ -6818,9 +6853,7 @@ torch::Tensor cont_head_bwd(const torch::Tensor& pre, const torch::Tensor& eps,
 // ---------------------------------------------------------------------------
 // Diagonal-Normal latent of Dreamer-V1 / Plan2Explore-DV1
 // (dreamer_v1.py compute_stochastic_state) and the KL between two such
-// latents, in the lane-group layout of the actor head above: a row owns an
-// aligned group of G lanes (cont_head_group), lane j keeps column j in
-// registers, S > 64 loops over columns with G = 64.  No LDS, no atomics.
+// latents, in the lane-group layout (group_row) over the S columns.
 //   gauss_state: pre = [N, 2S] (columns [0, S) mean a, [S, 2S) raw std b),
 //                sd = softplus(b) + min_std, x = a + sd*eps; mean and sd are
 //                stored in fp32 only where the caller wants them (the
@@ -6828,30 +6861,19 @@ torch::Tensor cont_head_bwd(const torch::Tensor& pre, const torch::Tensor& eps,
 //                saves pre and eps and recomputes:
 //                g_a = g_mean + g_x, g_b = (g_sd + g_x*eps) * sigmoid(b).
 //   normal_kl  : kl[row] = sum_j log(qs/ps) + (ps^2 + (pm-qm)^2)/(2 qs^2) - 1/2
-//                over four fp32 [N, S] inputs, a G-lane butterfly whose idle
-//                lanes hold 0; backward from the closed forms, one store
-//                stream per input that takes a gradient.
+//                over four fp32 [N, S] inputs, the group's sum; backward
+//                from the closed forms, one store stream per input that
+//                takes a gradient.
 // ---------------------------------------------------------------------------
-
-// overflow-safe softplus, as in cont_head_col
-template <typename T>
-__device__ __forceinline__ float tsoftplus(float z) {
-  if constexpr (sizeof(T) == 2)
-    return fmaxf(z, 0.f) + __logf(1.f + __expf(-fabsf(z)));
-  else
-    return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
-}
 
 // mean [N, S] and sd [N, S] are written only when STATS
 template <typename T, int G, bool STATS>
 __global__ void __launch_bounds__(256) NO_PACKED_FP32
     gauss_state_fwd_kernel(const T* __restrict__ pre, const float* __restrict__ eps, T* __restrict__ x,
                            float* __restrict__ mean, float* __restrict__ sd, long N, int S, float min_std) {
-  const int lane = threadIdx.x & (G - 1);
-  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  // groups past the last row recompute it and store nothing
-  const bool live = row < N;
-  if (!live) row = N - 1;
+  const int lane = group_lane<G>();
+  bool live;
+  const long row = group_row<G>(N, live);
   const T* pr = pre + row * 2L * S;
   const long base = row * (long)S;
   for (int j = lane; j < S; j += G) {
@@ -6874,9 +6896,10 @@ __global__ void __launch_bounds__(256) NO_PACKED_FP32
     gauss_state_bwd_kernel(const T* __restrict__ pre, const float* __restrict__ eps, const T* __restrict__ gx,
                            const float* __restrict__ gm, const float* __restrict__ gs, T* __restrict__ gpre,
                            long N, int S) {
-  const int lane = threadIdx.x & (G - 1);
-  const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  if (row >= N) return;  // no shuffles below: idle groups leave
+  const int lane = group_lane<G>();
+  bool live;
+  const long row = group_row<G>(N, live);
+  if (!live) return;  // no shuffles below: idle groups leave
   const T* pr = pre + row * 2L * S;
   T* gp = gpre + row * 2L * S;
   const long base = row * (long)S;
@@ -6893,12 +6916,9 @@ template <int G>
 __global__ void __launch_bounds__(256) NO_PACKED_FP32
     normal_kl_fwd_kernel(const float* __restrict__ pm, const float* __restrict__ ps, const float* __restrict__ qm,
                          const float* __restrict__ qs, float* __restrict__ kl, long N, int S) {
-  const int lane = threadIdx.x & (G - 1);
-  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  // groups past the last row recompute it and store nothing: every lane of
-  // the wave stays in the shuffles
-  const bool live = row < N;
-  if (!live) row = N - 1;
+  const int lane = group_lane<G>();
+  bool live;
+  const long row = group_row<G>(N, live);
   const long base = row * (long)S;
   float h = 0.f;
   for (int j = lane; j < S; j += G) {
@@ -6906,8 +6926,7 @@ __global__ void __launch_bounds__(256) NO_PACKED_FP32
     const float iq = 1.f / q;
     h += logf(q / p) + 0.5f * (p * p + d * d) * iq * iq - 0.5f;
   }
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) h += __shfl_xor(h, off, 64);
+  h = group_sum<G>(h);
   if (live && lane == 0) kl[row] = h;
 }
 
@@ -6918,14 +6937,13 @@ __global__ void __launch_bounds__(256) NO_PACKED_FP32
                          const float* __restrict__ qs, const float* __restrict__ gkl, float* __restrict__ gpm,
                          float* __restrict__ gps, float* __restrict__ gqm, float* __restrict__ gqs, long N,
                          int S) {
-  const int lane = threadIdx.x & (G - 1);
-  long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) / G;
-  const bool live = row < N;
-  if (!live) row = N - 1;
+  const int lane = group_lane<G>();
+  bool live;
+  const long row = group_row<G>(N, live);
   // the group's first lane reads the row's gradient for all of it
   float g = 0.f;
   if (lane == 0) g = gkl[row];
-  g = __shfl(g, (threadIdx.x & 63) & ~(G - 1), 64);
+  g = group_first<G>(g);
   if (!live) return;
   const long base = row * (long)S;
   for (int j = lane; j < S; j += G) {
@@ -6940,8 +6958,8 @@ __global__ void __launch_bounds__(256) NO_PACKED_FP32
   }
 }
 
-// Shape checks shared by both directions; returns (N, S, G, blocks).
-std::tuple<long, int, int, int> gauss_state_geometry(const torch::Tensor& pre, const torch::Tensor& eps) {
+// Shape checks shared by both directions; cols = S.
+LaneGroupGeometry gauss_state_geometry(const torch::Tensor& pre, const torch::Tensor& eps) {
   CHECK_IN(pre);
   CHECK_IN(eps);
   TORCH_CHECK(pre.dim() == 2 && pre.size(1) >= 2 && pre.size(1) % 2 == 0, "gauss_state: pre must be [N, 2S]");
@@ -6953,35 +6971,30 @@ std::tuple<long, int, int, int> gauss_state_geometry(const torch::Tensor& pre, c
   TORCH_CHECK(eps.scalar_type() == at::kFloat && eps.dim() == 2 && eps.size(0) == N && eps.size(1) == S,
               "gauss_state: eps must be fp32 [N, S]");
   TORCH_CHECK(eps.device() == pre.device(), "gauss_state: pre and eps must be on one device");
-  const int G = cont_head_group(N, S);
-  const long blocks = (N * G + kBlock - 1) / kBlock;
-  TORCH_CHECK(S <= INT_MAX / 2 && blocks <= INT_MAX, "gauss_state: shape too large for one launch");
-  return {N, (int)S, G, (int)blocks};
+  return lane_group_geometry("gauss_state", N, S, 2 * S);
 }
 
 // returns {sample} or, with want_stats, {sample, mean fp32, std fp32}
 std::vector<torch::Tensor> gauss_state_fwd(const torch::Tensor& pre, const torch::Tensor& eps, double min_std,
                                            bool want_stats) {
-  const auto [N, S, G, blocks] = gauss_state_geometry(pre, eps);
-  std::vector<torch::Tensor> out{torch::empty({N, (long)S}, pre.options())};
+  const auto geo = gauss_state_geometry(pre, eps);
+  const std::vector<long> shape{geo.N, (long)geo.cols};
+  std::vector<torch::Tensor> out{torch::empty(shape, pre.options())};
   if (want_stats) {
-    out.push_back(torch::empty({N, (long)S}, pre.options().dtype(at::kFloat)));
-    out.push_back(torch::empty({N, (long)S}, pre.options().dtype(at::kFloat)));
+    out.push_back(torch::empty(shape, pre.options().dtype(at::kFloat)));
+    out.push_back(torch::empty(shape, pre.options().dtype(at::kFloat)));
   }
-  if (N == 0) return out;
+  if (geo.N == 0) return out;
   float* mean = want_stats ? out[1].data_ptr<float>() : nullptr;
   float* sd = want_stats ? out[2].data_ptr<float>() : nullptr;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const long Nn = N;  // structured bindings do not capture into the dispatch lambdas
-  const int Sn = S, blk = blocks;
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pre.scalar_type(), "gauss_state_fwd", [&] {
     using T = scalar_t;
     with_bool(want_stats, [&](auto stats) {
-      with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
-        hipLaunchKernelGGL((gauss_state_fwd_kernel<T, decltype(group)::value, decltype(stats)::value>),
-                           dim3(blk), dim3(kBlock), 0, stream.stream(), (const T*)pre.data_ptr(),
-                           eps.data_ptr<float>(), (T*)out[0].data_ptr(), mean, sd, Nn, Sn, (float)min_std);
-      });
+      lane_group_launch(
+          geo,
+          [](auto group) { return gauss_state_fwd_kernel<T, decltype(group)::value, decltype(stats)::value>; },
+          (const T*)pre.data_ptr(), eps.data_ptr<float>(), (T*)out[0].data_ptr(), mean, sd, geo.N, geo.cols,
+          (float)min_std);
     });
   });
   return out;
@@ -6991,8 +7004,8 @@ torch::Tensor gauss_state_bwd(const torch::Tensor& pre, const torch::Tensor& eps
                               const c10::optional<torch::Tensor>& g_sample,
                               const c10::optional<torch::Tensor>& g_mean,
                               const c10::optional<torch::Tensor>& g_std) {
-  const auto [N, S, G, blocks] = gauss_state_geometry(pre, eps);
-  const long numel = N * S;
+  const auto geo = gauss_state_geometry(pre, eps);
+  const long numel = geo.N * geo.cols;
   // an absent gradient is a null pointer in the kernel
   auto grad_ptr = [&](const c10::optional<torch::Tensor>& g, at::ScalarType dtype, const char* what) {
     if (!g.has_value() || !g->defined()) return (const void*)nullptr;
@@ -7005,24 +7018,20 @@ torch::Tensor gauss_state_bwd(const torch::Tensor& pre, const torch::Tensor& eps
   const void* gm = grad_ptr(g_mean, at::kFloat, "g_mean must be contiguous fp32 [N, S]");
   const void* gs = grad_ptr(g_std, at::kFloat, "g_std must be contiguous fp32 [N, S]");
   auto gpre = torch::empty_like(pre);
-  if (N == 0) return gpre;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const long Nn = N;
-  const int Sn = S, blk = blocks;
+  if (geo.N == 0) return gpre;
   AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, pre.scalar_type(), "gauss_state_bwd", [&] {
     using T = scalar_t;
-    with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
-      hipLaunchKernelGGL((gauss_state_bwd_kernel<T, decltype(group)::value>), dim3(blk), dim3(kBlock), 0,
-                         stream.stream(), (const T*)pre.data_ptr(), eps.data_ptr<float>(), (const T*)gx,
-                         (const float*)gm, (const float*)gs, (T*)gpre.data_ptr(), Nn, Sn);
-    });
+    lane_group_launch(
+        geo, [](auto group) { return gauss_state_bwd_kernel<T, decltype(group)::value>; },
+        (const T*)pre.data_ptr(), eps.data_ptr<float>(), (const T*)gx, (const float*)gm, (const float*)gs,
+        (T*)gpre.data_ptr(), geo.N, geo.cols);
   });
   return gpre;
 }
 
-// Shape checks shared by both directions; returns (N, S, G, blocks).
-std::tuple<long, int, int, int> normal_kl_geometry(const torch::Tensor& pm, const torch::Tensor& ps,
-                                                   const torch::Tensor& qm, const torch::Tensor& qs) {
+// Shape checks shared by both directions; cols = S.
+LaneGroupGeometry normal_kl_geometry(const torch::Tensor& pm, const torch::Tensor& ps, const torch::Tensor& qm,
+                                     const torch::Tensor& qs) {
   CHECK_IN(pm);
   CHECK_IN(ps);
   CHECK_IN(qm);
@@ -7031,28 +7040,18 @@ std::tuple<long, int, int, int> normal_kl_geometry(const torch::Tensor& pm, cons
   for (const torch::Tensor* t : {&pm, &ps, &qm, &qs})
     TORCH_CHECK(t->scalar_type() == at::kFloat && t->sizes() == pm.sizes() && t->device() == pm.device(),
                 "normal_kl: pm, ps, qm, qs must be fp32 tensors of one shape on one device");
-  const long N = pm.size(0);
-  const long S = pm.size(1);
-  const int G = cont_head_group(N, S);
-  const long blocks = (N * G + kBlock - 1) / kBlock;
-  TORCH_CHECK(S <= INT_MAX && blocks <= INT_MAX, "normal_kl: shape too large for one launch");
-  return {N, (int)S, G, (int)blocks};
+  return lane_group_geometry("normal_kl", pm.size(0), pm.size(1), pm.size(1));
 }
 
 // per-row KL(N(pm, ps) || N(qm, qs)) summed over the columns, fp32 [N]
 torch::Tensor normal_kl_fwd(const torch::Tensor& pm, const torch::Tensor& ps, const torch::Tensor& qm,
                             const torch::Tensor& qs) {
-  const auto [N, S, G, blocks] = normal_kl_geometry(pm, ps, qm, qs);
-  auto kl = torch::empty({N}, pm.options());
-  if (N == 0) return kl;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const long Nn = N;
-  const int Sn = S, blk = blocks;
-  with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
-    hipLaunchKernelGGL((normal_kl_fwd_kernel<decltype(group)::value>), dim3(blk), dim3(kBlock), 0,
-                       stream.stream(), pm.data_ptr<float>(), ps.data_ptr<float>(), qm.data_ptr<float>(),
-                       qs.data_ptr<float>(), kl.data_ptr<float>(), Nn, Sn);
-  });
+  const auto geo = normal_kl_geometry(pm, ps, qm, qs);
+  auto kl = torch::empty({geo.N}, pm.options());
+  if (geo.N == 0) return kl;
+  lane_group_launch(
+      geo, [](auto group) { return normal_kl_fwd_kernel<decltype(group)::value>; }, pm.data_ptr<float>(),
+      ps.data_ptr<float>(), qm.data_ptr<float>(), qs.data_ptr<float>(), kl.data_ptr<float>(), geo.N, geo.cols);
   return kl;
 }
 
@@ -7062,9 +7061,9 @@ std::vector<torch::Tensor> normal_kl_bwd(const torch::Tensor& pm, const torch::T
                                          const torch::Tensor& qm, const torch::Tensor& qs,
                                          const torch::Tensor& g_kl, bool need_pm, bool need_ps, bool need_qm,
                                          bool need_qs) {
-  const auto [N, S, G, blocks] = normal_kl_geometry(pm, ps, qm, qs);
+  const auto geo = normal_kl_geometry(pm, ps, qm, qs);
   CHECK_IN(g_kl);
-  TORCH_CHECK(g_kl.scalar_type() == at::kFloat && g_kl.numel() == N && g_kl.device() == pm.device(),
+  TORCH_CHECK(g_kl.scalar_type() == at::kFloat && g_kl.numel() == geo.N && g_kl.device() == pm.device(),
               "normal_kl_bwd: g_kl must be fp32 [N]");
   const bool need[4] = {need_pm, need_ps, need_qm, need_qs};
   std::vector<torch::Tensor> out(4);
@@ -7072,17 +7071,13 @@ std::vector<torch::Tensor> normal_kl_bwd(const torch::Tensor& pm, const torch::T
   for (int i = 0; i < 4; ++i) {
     if (!need[i]) continue;
     out[i] = torch::empty_like(pm);
-    ptr[i] = N > 0 ? out[i].data_ptr<float>() : nullptr;
+    ptr[i] = geo.N > 0 ? out[i].data_ptr<float>() : nullptr;
   }
-  if (N == 0) return out;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const long Nn = N;
-  const int Sn = S, blk = blocks;
-  with_int<4, 8, 16, 32, 64>(G, [&](auto group) {
-    hipLaunchKernelGGL((normal_kl_bwd_kernel<decltype(group)::value>), dim3(blk), dim3(kBlock), 0,
-                       stream.stream(), pm.data_ptr<float>(), ps.data_ptr<float>(), qm.data_ptr<float>(),
-                       qs.data_ptr<float>(), g_kl.data_ptr<float>(), ptr[0], ptr[1], ptr[2], ptr[3], Nn, Sn);
-  });
+  if (geo.N == 0) return out;
+  lane_group_launch(
+      geo, [](auto group) { return normal_kl_bwd_kernel<decltype(group)::value>; }, pm.data_ptr<float>(),
+      ps.data_ptr<float>(), qm.data_ptr<float>(), qs.data_ptr<float>(), g_kl.data_ptr<float>(), ptr[0], ptr[1],
+      ptr[2], ptr[3], geo.N, geo.cols);
   return out;
 }
 

@@ -412,6 +412,16 @@ def _cont_head_torch(pre: Tensor, eps: Tensor, mode: str, init_std: float, min_s
     return x.to(pre.dtype), entropy
 
 
+def _rows(t: Tensor, cols: int) -> Tensor:
+    """``t`` flattened to the contiguous [N, cols] that the lane-group kernels take."""
+    return t.reshape(-1, cols).contiguous()
+
+
+def _grad(g: Optional[Tensor], dtype: torch.dtype = torch.float32) -> Optional[Tensor]:
+    """An incoming gradient, contiguous in ``dtype``; an absent one stays None."""
+    return None if g is None else g.to(dtype).contiguous()
+
+
 class _ContinuousActorHead(torch.autograd.Function):
     """Fused continuous actor head of the Dreamer family: reparameterized
     sample, action clip and per-row entropy in one kernel each way.  Saves
@@ -430,11 +440,7 @@ class _ContinuousActorHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_actions: Optional[Tensor], g_entropy: Optional[Tensor]):
         pre, eps = ctx.saved_tensors
-        if g_actions is not None:
-            g_actions = g_actions.to(pre.dtype).contiguous()
-        if g_entropy is not None:
-            g_entropy = g_entropy.float().contiguous()
-        g_pre = require_ext().cont_head_bwd(pre, eps, g_actions, g_entropy, *ctx.meta)
+        g_pre = require_ext().cont_head_bwd(pre, eps, _grad(g_actions, pre.dtype), _grad(g_entropy), *ctx.meta)
         return g_pre, None, None, None, None, None, None
 
 
@@ -457,8 +463,7 @@ def continuous_actor_head(pre: Tensor, eps: Tensor, mode: str, init_std: float, 
     if not use_hip(pre):
         return _cont_head_torch(pre, eps, mode, *args)
     actions, entropy = _ContinuousActorHead.apply(
-        pre.reshape(-1, 2 * A).contiguous(), eps.detach().float().reshape(-1, A).contiguous(),
-        _CONT_HEAD_MODES[mode], *args,
+        _rows(pre, 2 * A), _rows(eps.detach().float(), A), _CONT_HEAD_MODES[mode], *args,
     )
     return actions.view(*lead, A), (entropy.view(lead) if entropy is not None else None)
 
@@ -489,13 +494,8 @@ class _GaussianState(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_sample: Optional[Tensor], g_mean: Optional[Tensor], g_std: Optional[Tensor]):
         pre, eps = ctx.saved_tensors
-        if g_sample is not None:
-            g_sample = g_sample.to(pre.dtype).contiguous()
-        if g_mean is not None:
-            g_mean = g_mean.float().contiguous()
-        if g_std is not None:
-            g_std = g_std.float().contiguous()
-        return require_ext().gauss_state_bwd(pre, eps, g_sample, g_mean, g_std), None, None, None
+        g_pre = require_ext().gauss_state_bwd(pre, eps, _grad(g_sample, pre.dtype), _grad(g_mean), _grad(g_std))
+        return g_pre, None, None, None
 
 
 def gaussian_state(pre: Tensor, eps: Tensor, min_std: float,
@@ -512,8 +512,7 @@ def gaussian_state(pre: Tensor, eps: Tensor, min_std: float,
     if not use_hip(pre):
         return _gauss_state_torch(pre, eps, float(min_std), want_stats)
     sample, mean, std = _GaussianState.apply(
-        pre.reshape(-1, 2 * S).contiguous(), eps.detach().float().reshape(-1, S).contiguous(),
-        float(min_std), bool(want_stats),
+        _rows(pre, 2 * S), _rows(eps.detach().float(), S), float(min_std), bool(want_stats),
     )
     if not want_stats:
         return sample.view(*lead, S), None, None
@@ -539,7 +538,7 @@ class _NormalKL(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_kl: Tensor):
         grads = require_ext().normal_kl_bwd(
-            *ctx.saved_tensors, g_kl.float().contiguous(), *ctx.needs_input_grad[:4]
+            *ctx.saved_tensors, _grad(g_kl), *ctx.needs_input_grad[:4]
         )
         return tuple(grads)
 
@@ -553,7 +552,7 @@ def normal_kl(pm: Tensor, ps: Tensor, qm: Tensor, qs: Tensor) -> Tensor:
         raise ValueError(f"normal_kl: shapes {[tuple(t.shape) for t in (pm, ps, qm, qs)]} do not match")
     if not use_hip(pm):
         return _normal_kl_torch(pm, ps, qm, qs)
-    return _NormalKL.apply(*(t.float().reshape(-1, S).contiguous() for t in (pm, ps, qm, qs))).view(lead)
+    return _NormalKL.apply(*(_rows(t.float(), S) for t in (pm, ps, qm, qs))).view(lead)
 
 
 class _PPOLosses(torch.autograd.Function):

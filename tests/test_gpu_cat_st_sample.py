@@ -95,3 +95,30 @@ def test_rollout_same_with_sampler_and_cat_st_fwd_o(monkeypatch):
     assert torch.equal(acts1, acts0)
     zs = traj1[1:, :, :SK].reshape(HZ, B, S, K).float()
     assert torch.equal(zs.sum(-1), torch.ones(HZ, B, S, device="cuda"))
+
+
+@requires_gpu
+def test_idle_groups_store_nothing():
+    """bf16, K=9 is G=16, four rows to a wave: with 5 rows the second wave has
+    three idle groups.  They recompute the last row and must store nothing, so
+    the rows after the 5 handed to the kernel keep their sentinel bit for bit."""
+    from sheeprl_amd.ops._ext import require_ext
+
+    ext = require_ext()
+    rows, total, K = 5, 9, 9
+    assert ext.cont_head_route(rows, K) == 16
+    torch.manual_seed(59)
+    raw = (torch.randn(rows, K, device="cuda") * 3).to(torch.bfloat16)
+    urand = torch.rand(rows, K, device="cuda")
+    unimix = 0.01
+
+    m = torch.empty(rows, K, device="cuda", dtype=torch.float32)
+    s = torch.empty(rows, K, device="cuda", dtype=torch.float32)
+    expect = torch.empty(rows, K, device="cuda", dtype=torch.bfloat16)
+    ext.cat_st_fwd_o(raw, urand, unimix, m, expect, s)
+
+    buf = torch.full((total, K), -7.5, device="cuda", dtype=torch.bfloat16)
+    sentinel = buf[rows:].clone()
+    ext.cat_st_sample_o(raw, urand, unimix, buf[:rows])
+    assert torch.equal(buf[rows:].view(torch.int16), sentinel.view(torch.int16))
+    assert torch.equal(buf[:rows], expect)

@@ -142,3 +142,14 @@ def test_gru_route_invariants(ext):
                 assert not backward and N > 64 and H % (16 // itemsize) == 0, where
             else:
                 assert kind == "ROW", where
+
+
+def test_lane_group_width_rule(ext):
+    """The one group-width rule of the lane-group kernels (cont_head,
+    gauss_state, normal_kl, cat_st_sample): the next power of two >= cols
+    within [4, 64]."""
+    for cols in range(1, 201):
+        G = ext.cont_head_route(1024, cols)
+        assert G in {4, 8, 16, 32, 64}, cols
+        assert G >= min(cols, 64), (cols, G)
+        assert G == 4 or G // 2 < cols, (cols, G)
